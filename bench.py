@@ -1,14 +1,22 @@
 #!/usr/bin/env python3
 """Benchmark of the YOLOv1 hot path on MI355X.  Prints ONE JSON line (rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--no-train] [--no-cpu] [--no-resnet]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 64] [--dump-outputs DIR]
+                    [--full [--no-train] [--no-cpu] [--no-nms] [--no-resnet] [--layers] [--sustain-s S]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 metric / value : images/sec of the forward pass of YOLOv1 (24-conv backbone + FC head) on synthetic
                  448x448 batches of `--batch` (64) images per GPU, inputs resident in HBM, bf16 storage /
-                 fp32 MFMA accumulation -- BASELINE.json configs[1].  A "step" = one forward over one batch.
-extra keys     : "train" = forward + YOLOLoss + backward + clip + Adam step (configs[2]; with N > 1 the
+                 fp32 MFMA accumulation -- BASELINE.json configs[1].  A "step" = one forward over one batch;
+                 "ms_per_step" = milliseconds of one of the K timed steps.
+plain run      : set-up, one untimed first forward (weight packing, workspaces), W warm-up + K timed steps, the
+                 outputs (--dump-outputs), the JSON line.  Every extra key below is null unless --full is given.
+--dump-outputs : rank 0 writes the predictions of its last timed step as DIR/predictions.npy (float32,
+                 [batch, 7, 7, 30]); the inputs and weights are seeded, so runs with the same arguments compare
+                 output for output.
+extra keys     : (--full) "sustained" = the forward over >= 200 steps;
+                 "train" = forward + YOLOLoss + backward + clip + Adam step (configs[2]; with N > 1 the
                  gradients are all-reduced over RCCL: configs[3]);  "nms" = decode + per-image NMS boxes/sec
                  (configs[4]'s post-processing);  "roofline" for the dominant kernel (implicit-GEMM MFMA
                  kernel, forward launches);  "cpu_baseline" = the stock-torch CPU restatement of the
@@ -196,7 +204,12 @@ def main():
     ap.add_argument("--layers", action="store_true", help="print the per-layer kernel table to stderr")
     ap.add_argument("--no-resnet", action="store_true", help="skip BASELINE configs[4] (ResNet50 variant: batch 64 inference + NMS, and its training step)")
     ap.add_argument("--sustain-s", type=float, default=2.0, help="length of the sustained forward measurement in seconds (>= 200 steps)")
+    ap.add_argument("--full", action="store_true", help="also measure everything beyond the headline forward: sustained forward, roofline, train step, "
+                    "NMS, preprocessing, small batches, ResNet50 variant, CPU baselines (the --no-* and --layers options select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the predictions of the last timed step to DIR/predictions.npy")
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
     if a.gpus > 1 and "RANK" not in os.environ:
         _launch_ranks(a.gpus)
@@ -206,7 +219,7 @@ def main():
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != a.gpus:
         raise SystemExit(f"--gpus {a.gpus} but WORLD_SIZE={world}")
-    # BENCH_REHEARSE=1: the whole N-rank code path (launcher, sharded inputs, gradient arena + bucketed all-reduce, max-over-ranks timing,
+    # BENCH_REHEARSE=1 (with --full): the whole N-rank code path (launcher, sharded inputs, gradient arena + bucketed all-reduce, max-over-ranks timing,
     # rank-0 JSON) on a box with ONE GPU -- every rank on device 0, gloo instead of RCCL (which refuses to use a device twice).  The numbers
     # mean nothing (the ranks share the GPU); the run shows that the path works.  Marked in the JSON line.
     rehearse = os.environ.get("BENCH_REHEARSE") == "1"
@@ -251,10 +264,12 @@ def main():
 
     # ---------------------------------------------------------------- forward (the headline value)
     model.eval()
+    last = {}
 
     def fwd():
         with torch.no_grad():
-            return model(x)
+            last["predictions"] = model(x)      # what a caller of the timed path receives (kept for --dump-outputs)
+            return last["predictions"]
 
     # first forward of the process: weight packing, workspace allocation, library load -- no tuning (the launch plans ship
     # with the package); reported, not part of any timed region
@@ -266,15 +281,22 @@ def main():
 
     dt_f = timed_steps(fwd, a.steps, a.warmup, world)
     fwd_ips = world * B * a.steps / dt_f
-    # the driver's K steps last ~0.06 s; the same measurement sustained over >= 200 steps and >= --sustain-s seconds
-    n_sus = max(200, int(a.sustain_s / max(dt_f / a.steps, 1e-6)))
-    dt_s = timed_steps(fwd, n_sus, 0, world)
-    sustained = {"value": round(world * B * n_sus / dt_s, 1), "unit": "images/s", "steps": n_sus, "seconds": round(dt_s, 3), "ms_per_step": round(1e3 * dt_s / n_sus, 3)}
+    if a.dump_outputs and rank == 0:
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "predictions.npy"), last["predictions"].float().cpu().numpy())
+
+    # ---------------------------------------------------------------- sustained forward (--full)
+    sustained = None
+    if a.full:
+        # the driver's K steps last ~0.06 s; the same measurement sustained over >= 200 steps and >= --sustain-s seconds
+        n_sus = max(200, int(a.sustain_s / max(dt_f / a.steps, 1e-6)))
+        dt_s = timed_steps(fwd, n_sus, 0, world)
+        sustained = {"value": round(world * B * n_sus / dt_s, 1), "unit": "images/s", "steps": n_sus, "seconds": round(dt_s, 3), "ms_per_step": round(1e3 * dt_s / n_sus, 3)}
 
     # ---------------------------------------------------------------- roofline of the dominant kernel
     roof = None
     layer_rows = []
-    if rank == 0:
+    if a.full and rank == 0:
         engine.TIMERS = []
         reps = 3
         launches0 = engine.IGEMM_LAUNCHES
@@ -317,7 +339,7 @@ def main():
 
     # ---------------------------------------------------------------- train step
     train = None
-    if not a.no_train:
+    if a.full and not a.no_train:
         model.train()
         crit = YOLOLoss()
         from yolo.optim import Adam
@@ -412,7 +434,7 @@ def main():
 
     # ---------------------------------------------------------------- decode + NMS
     nms = None
-    if not a.no_nms and rank == 0:
+    if a.full and not a.no_nms and rank == 0:
         p01 = torch.from_numpy(np.random.Generator(np.random.PCG64([0, 99])).uniform(0, 1, size=(64, 7, 7, 30)).astype(np.float32)).to(dev)
 
         def post():
@@ -431,7 +453,7 @@ def main():
 
     # ---------------------------------------------------------------- preprocessing on the device
     pre = None
-    if not a.no_nms and rank == 0:
+    if a.full and not a.no_nms and rank == 0:
         from yolo.preprocess import preprocess_u8
         u8 = torch.from_numpy(np.random.Generator(np.random.PCG64([0, 5])).integers(0, 256, size=(64, 375, 500, 3), dtype=np.uint8)).to(dev)
 
@@ -453,7 +475,7 @@ def main():
 
     # ---------------------------------------------------------------- small batches: predict.py's single image (configs[0] runs it on the CPU), evaluate.py's 16
     small = None
-    if rank == 0 and world == 1 and not a.no_nms:
+    if a.full and rank == 0 and world == 1 and not a.no_nms:
         small = {"unit": "ms per forward (YOLOv1Backbone + FC head, inputs resident, back-to-back forwards)",
                  "note": "yolo/plans/gfx950.json holds measured plans for batches 1, 2, 4, 8, 16, 32 and 64; few-pixel deep-K layers split their K range over the chip (DESIGN.md section 7)"}
         model.eval()
@@ -472,7 +494,7 @@ def main():
 
     # ---------------------------------------------------------------- ResNet50 variant (configs[4])
     resnet = None
-    if not a.no_resnet and rank == 0 and world == 1:
+    if a.full and not a.no_resnet and rank == 0 and world == 1:
         from yolo import ResNetBackbone
         del model
         torch.cuda.empty_cache()
@@ -516,7 +538,7 @@ def main():
 
     # ---------------------------------------------------------------- CPU baseline (rank 0, N=1 only)
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu:
         from oracle import oracle as O
         from oracle.torch_ref import RefYOLOv1
         ref = RefYOLOv1().eval()

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""From `rocprofv3 --kernel-trace --output-format csv -- python3 bench.py`: duration of the yolo_igemm launches of bench.py's
+"""From `rocprofv3 --kernel-trace --output-format csv -- python3 bench.py --full`: duration of the yolo_igemm launches of bench.py's
 roofline pass (3 forward passes, bracketed by two yolo::sumsq_kernel marker launches), for comparison with bench.py's own
 HIP-event numbers (roofline.avg_launch_ms / kernel_ms_per_step).  usage: trace_roofline.py <kernel_trace.csv>"""
 import csv, sys

@@ -32,4 +32,4 @@ print(json.dumps({
     "hbm_read_bytes_per_launch": fetch / launches, "hbm_write_bytes_per_launch": write / launches,
     "hbm_bytes_per_launch": (fetch + write) / launches,
     "correction": "FETCH_SIZE x2 (gfx950 half-count of wide coalesced reads), KiB -> bytes; WRITE_SIZE exact",
-    "command": "rocprofv3 --pmc <C> -- python3 " + ("tools/train_steps.py 3" if WG else "bench.py --steps 3 --warmup 1 --no-train --no-nms --no-cpu --no-resnet") + " (separate passes)"}))
+    "command": "rocprofv3 --pmc <C> -- python3 " + ("tools/train_steps.py 3" if WG else "bench.py --full --steps 3 --warmup 1 --no-train --no-nms --no-cpu --no-resnet") + " (separate passes)"}))
