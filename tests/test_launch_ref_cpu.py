@@ -1,0 +1,258 @@
+"""The fp64 launch reference of tests/launch_ref.py against stock torch on small problems (no GPU): forward convs at stride 1 / 2 with padded channel
+strides, the parity classes of a stride-2 data gradient, every epilogue, the fused pool and its arg-max codes, both weight-gradient forms -- and three
+sabotaged outputs the checker must reject."""
+
+from types import SimpleNamespace
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import launch_ref as lr
+
+BF = torch.bfloat16
+
+
+class Buf:
+    """zero-haloed NHWC bf16 buffer [N][H+2h][W+2h][Cp] (Cp >= C channels) between guard bands of zeros, as engine.Act lays it out"""
+
+    def __init__(self, N, H, W, C, halo=1, cpad=None, dtype=BF):
+        self.N, self.H, self.W, self.C, self.h = N, H, W, C, halo
+        self.Cp = cpad or C
+        self.Hp, self.Wp = H + 2 * halo, W + 2 * halo
+        self.px, self.row, self.img = self.Cp, self.Wp * self.Cp, self.Hp * self.Wp * self.Cp
+        self.guard = (self.Wp + 2) * self.Cp + 64
+        self.store = torch.zeros(2 * self.guard + N * self.img, dtype=dtype)
+
+    def region(self):
+        return self.store[self.guard: self.guard + self.N * self.img]
+
+    def view(self):
+        return self.region().view(self.N, self.Hp, self.Wp, self.Cp)
+
+    def interior(self):
+        h = self.h
+        return self.view()[:, h: h + self.H, h: h + self.W, : self.C]
+
+    def off(self, shift=0):
+        h = self.h - shift
+        return (h * self.Wp + h) * self.Cp
+
+    def fill(self, x_nchw):
+        self.interior().copy_(x_nchw.permute(0, 2, 3, 1).to(self.store.dtype))
+        return self
+
+
+def _bf(t):
+    return t.to(BF).double()
+
+
+def _desc(**kw):
+    base = dict(epilogue=0, slope=0.1, out_fp32=0, split_k=1, aux_img_stride=0, aux_row_stride=0, aux_px_stride=0, aux_off=0, pool2=0)
+    base.update(kw)
+    return SimpleNamespace(**base)
+
+
+def _conv_desc(xb, ob, k, s, cout, **kw):
+    pad = (k - 1) // 2
+    Ho, Wo = (xb.H + 2 * pad - k) // s + 1, (xb.W + 2 * pad - k) // s + 1
+    return _desc(N=xb.N, Ho=Ho, Wo=Wo, in_img_stride=xb.img, in_row_stride=xb.row, in_px_stride=xb.px, in_off=xb.off(pad), stride=s, KH=k, KW=k,
+                 tap_len=xb.C, Cout=cout, out_img_stride=ob.img, out_row_stride=ob.row, out_px_stride=ob.px, out_off=ob.off(), **kw)
+
+
+def _packed(w):
+    """OIHW -> [Cout][KH][KW][Cin] flat bf16, the forward operand"""
+    return w.permute(0, 2, 3, 1).contiguous().to(BF).reshape(-1)
+
+
+def _store(ob, y_nhwc):
+    """a kernel's output as the checker reads it: the whole region, y written into the interior"""
+    got = ob.region().clone()
+    h = ob.h
+    got.view(ob.N, ob.Hp, ob.Wp, ob.Cp)[:, h: h + y_nhwc.shape[1], h: h + y_nhwc.shape[2], : y_nhwc.shape[3]] = y_nhwc.to(BF)
+    return got
+
+
+def _problem(seed, N, H, cin, cout, k, s, cpad_in, cpad_out):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, cin, H, H, generator=g)
+    w = torch.randn(cout, cin, k, k, generator=g) / (cin * k * k) ** 0.5
+    xb = Buf(N, H, H, cin, 1, cpad_in).fill(x)
+    if cpad_in > cin:           # channel padding of the input holds garbage the launch must not read
+        xb.view()[..., cin:] = 7.0
+    Ho = (H + 2 * ((k - 1) // 2) - k) // s + 1
+    ob = Buf(N, Ho, Ho, cout, 1, cpad_out)
+    return x, w, xb, ob
+
+
+@pytest.mark.parametrize("k,s", [(3, 1), (3, 2), (1, 1), (1, 2)])
+def test_forward_equals_conv2d_with_padded_channel_strides(k, s):
+    x, w, xb, ob = _problem(1 + k + s, 2, 8, 24, 40, k, s, 32, 48)
+    d = _conv_desc(xb, ob, k, s, 40)
+    R = lr.igemm_ref(d, xb.store, xb.guard, _packed(w))
+    want = F.conv2d(_bf(x), _bf(w), stride=s, padding=(k - 1) // 2).permute(0, 2, 3, 1)
+    got_ref = lr._out_view(R.ref, d)
+    assert torch.allclose(got_ref, want, rtol=1e-12, atol=1e-12)
+    # exactly the interior's first Cout channels are addressed: halo and channel padding are not
+    assert int(R.addressed.sum()) == want.numel()
+    assert bool(lr._out_view(R.addressed, d).all())
+    # a float32 result rounded to bf16 (what a correct kernel stores) lies inside the bound
+    worst, fails = R.check(_store(ob, F.conv2d(x.to(BF).float(), w.to(BF).float(), stride=s, padding=(k - 1) // 2).permute(0, 2, 3, 1)), what="conv")
+    assert not fails and 0.0 < worst <= 1.0
+
+
+@pytest.mark.parametrize("epi", [1, 2, 3, 4])
+def test_epilogues(epi):
+    x, w, xb, ob = _problem(10 + epi, 2, 8, 16, 24, 3, 1, 16, 32)
+    g = torch.Generator().manual_seed(99)
+    bias = torch.randn(24, generator=g)
+    a = torch.randn(2, 24, 8, 8, generator=g)
+    ab = Buf(2, 8, 8, 24, 1, 40).fill(a)
+    d = _conv_desc(xb, ob, 3, 1, 24, epilogue=epi, slope=0.1 if epi != 4 else 0.0,
+                   aux_img_stride=ab.img, aux_row_stride=ab.row, aux_px_stride=ab.px, aux_off=ab.off())
+    R = lr.igemm_ref(d, xb.store, xb.guard, _packed(w), bias, ab.store, ab.guard)
+    z = F.conv2d(_bf(x), _bf(w), padding=1)
+    av = _bf(a)
+    if epi == 1:
+        want = z + bias.double()[None, :, None, None]
+    elif epi == 2:
+        want = F.leaky_relu(z + bias.double()[None, :, None, None], 0.1)
+    elif epi == 3:
+        want = z * torch.where(av > 0, 1.0, 0.1)
+    else:
+        want = F.relu(z + bias.double()[None, :, None, None] + av)
+    assert torch.allclose(lr._out_view(R.ref, d), want.permute(0, 2, 3, 1), rtol=1e-12, atol=1e-12)
+    worst, fails = R.check(_store(ob, want.float().permute(0, 2, 3, 1)))
+    assert not fails and worst <= 1.0
+
+
+@pytest.mark.parametrize("pool2", [1, 2, 3])
+def test_fused_pool_and_argmax_codes(pool2):
+    x, w, xb, ob = _problem(30 + pool2, 2, 8, 16, 24, 3, 1, 16, 24)
+    ob = Buf(2, 4, 4, 24, 1, 32)
+    full = Buf(2, 8, 8, 24, 1, 24)
+    bias = torch.linspace(-0.5, 0.5, 24)
+    d = _conv_desc(xb, ob, 3, 1, 24, epilogue=2, pool2=pool2)
+    if pool2 == 2:
+        d.aux_img_stride, d.aux_row_stride, d.aux_px_stride, d.aux_off = full.img, full.row, full.px, full.off()
+    R = lr.igemm_ref(d, xb.store, xb.guard, _packed(w), bias)
+    act = F.leaky_relu(F.conv2d(_bf(x), _bf(w), bias.double(), padding=1), 0.1)
+    pooled, idx = F.max_pool2d(act, 2, 2, return_indices=True)
+    assert torch.allclose(lr._out_view(R.ref, d, pooled=True), pooled.permute(0, 2, 3, 1), rtol=1e-12, atol=1e-12)
+    assert int(R.addressed.sum()) == pooled.numel()
+    got = _store(ob, pooled.float().permute(0, 2, 3, 1))
+    if pool2 == 1:
+        worst, fails = R.check(got)
+    elif pool2 == 2:
+        assert torch.allclose(lr._aux_view(R.aux_ref, d), act.permute(0, 2, 3, 1), rtol=1e-12, atol=1e-12)
+        worst, fails = R.check(got, got_aux=_store(full, act.float().permute(0, 2, 3, 1)))
+    else:
+        # codes as F.max_pool2d's indices give them: window position 2 * dy + dx, 2 bits per channel, uint16 per 8 channels at (pooled address) / 8
+        H = 8
+        iy, ix = idx // H, idx % H
+        pos = ((iy % 2) * 2 + (ix % 2)).permute(0, 2, 3, 1)            # [N][4][4][C]
+        codes = torch.zeros(ob.N * ob.img // 8, dtype=torch.int32)
+        addr = lr._out_view(torch.arange(ob.N * ob.img), d, pooled=True)
+        codes.index_put_((addr.reshape(-1) // 8,), (pos.reshape(-1).int() << (2 * (addr.reshape(-1) % 8)).int()), accumulate=True)
+        worst, fails = R.check(got, got_codes=codes.to(torch.int16))
+        assert not fails
+        # a wrong position in a window whose maximum is clear is rejected
+        vals = R.codes_vals
+        top = vals.topk(2, dim=1).values
+        clear = int(torch.nonzero((top[:, 0] - top[:, 1]) > 0.05).flatten()[0])
+        w_i, sh = int(R.codes_idx[clear]), int(R.codes_shift[clear])
+        bad = codes.clone()
+        bad[w_i] ^= 1 << sh
+        assert R.check(got, got_codes=bad.to(torch.int16))[1]
+    assert not fails and worst <= 1.0
+
+
+@pytest.mark.parametrize("halo_w", [0, 1])
+def test_stride2_data_gradient_by_parity_class(halo_w):
+    """the data gradient of a stride-2 3x3 conv as four small convs over the non-zero slots of the zero-stuffed gradient (1x1, 1x2, 2x1 and 2x2 taps),
+    each writing its parity class of the input gradient through doubled strides (out_px_stride = 2 * Cout)"""
+    N, H, cin, cout = 2, 8, 16, 24
+    g = torch.Generator().manual_seed(5 + halo_w)
+    w = torch.randn(cout, cin, 3, 3, generator=g)
+    dy = torch.randn(N, cout, H // 2, H // 2, generator=g)
+    want = F.conv_transpose2d(_bf(dy), _bf(w), stride=2, padding=1, output_padding=1)          # [N][cin][H][H]
+    gb = Buf(N, H, H, cout, 1)                      # dy zero-stuffed on the input grid
+    gb.interior()[:, ::2, ::2, :] = dy.permute(0, 2, 3, 1).to(BF)
+    ob = Buf(N, H, H, cin, 1, cin + 8 * halo_w)
+    wd = w.permute(1, 2, 3, 0).flip(1, 2)           # [cin][ky'][kx'][cout], ky' = 2 - ky
+    sel = {0: [1], 1: [0, 2]}
+    seen = torch.zeros(N * ob.img, dtype=torch.int32)
+    total = torch.full((N * ob.img,), float("nan"), dtype=torch.float64)
+    for py in (0, 1):
+        for px in (0, 1):
+            wc = wd[:, sel[py]][:, :, sel[px]].contiguous().to(BF).reshape(-1)
+            d = _desc(N=N, Ho=H // 2, Wo=H // 2, in_img_stride=gb.img, in_row_stride=2 * gb.row, in_px_stride=2 * gb.px, in_off=gb.off(), stride=1,
+                      KH=1 + py, KW=1 + px, tap_len=cout, Cout=cin, out_img_stride=ob.img, out_row_stride=2 * ob.row, out_px_stride=2 * ob.px,
+                      out_off=ob.off() + py * ob.row + px * ob.px)
+            R = lr.igemm_ref(d, gb.store, gb.guard, wc)
+            seen += R.addressed.int()
+            total[R.addressed] = R.ref[R.addressed]
+    assert int(seen.max()) == 1 and int(seen.sum()) == want.numel()         # the four classes tile the interior
+    got = total.view(N, ob.Hp, ob.Wp, ob.Cp)[:, 1: 1 + H, 1: 1 + H, :cin]
+    assert torch.allclose(got, want.permute(0, 2, 3, 1), rtol=1e-12, atol=1e-12)
+
+
+def _wgrad_problem(seed, N, H, cin, cout, s, cpad_in, cpad_dy):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, cin, H, H, generator=g)
+    w = torch.randn(cout, cin, 3, 3, generator=g)
+    gy = torch.randn(N, cout, H // s, H // s, generator=g)
+    xd = _bf(x).requires_grad_(True)
+    wd = _bf(w).requires_grad_(True)
+    F.conv2d(xd, wd, stride=s, padding=1).backward(_bf(gy))
+    xb = Buf(N, H, H, cin, 1, cpad_in).fill(x)
+    gb = Buf(N, H, H, cout, 1, cpad_dy)                 # dy in the input's geometry (zero-stuffed for stride 2)
+    gb.interior()[:, ::s, ::s, :] = gy.permute(0, 2, 3, 1).to(BF)
+    return wd.grad.permute(0, 2, 3, 1).reshape(cout, -1), _bf(gy).sum((0, 2, 3)), xb, gb
+
+
+@pytest.mark.parametrize("geo,s", [(False, 1), (True, 1), (True, 2)])
+def test_weight_gradient_equals_autograd(geo, s):
+    N, H, cin, cout = 2, 8, 16, 24
+    want_dw, want_db, xb, gb = _wgrad_problem(40 + s + geo, N, H, cin, cout, s, 24, 32)
+    d = SimpleNamespace(P=N * xb.Hp * xb.Wp, dy_px_stride=gb.px, x_px_stride=xb.px, Cout=cout, Cin=cin, KH=3, KW=3, pad=1, x_row_stride=xb.row,
+                        geo_W=0)
+    if geo:
+        d.P, d.geo_W, d.geo_H = N * (H // s) ** 2, H // s, H // s
+        d.geo_img_slots, d.geo_row_slots, d.geo_px_slots, d.geo_slot0 = xb.Hp * xb.Wp, s * xb.Wp, s, xb.Wp + 1
+    lo, hi = lr.wgrad_extent(d, "x")
+    assert -lo <= xb.guard and hi <= xb.guard + N * xb.img            # (the flat form reads into the guard bands)
+    dw, db = lr.wgrad_ref(d, xb.store, xb.guard, gb.store, gb.guard)
+    assert torch.allclose(dw, want_dw, rtol=1e-12, atol=1e-10)
+    assert torch.allclose(db, want_db, rtol=1e-12, atol=1e-10)
+    # a float32 result is inside the per-tensor bound, one pixel range of eight left out is not
+    assert lr.rel_l2(dw.float(), want_dw) < 1e-6
+    if geo:
+        d.P = N * (H // s) ** 2 * 7 // 8
+        assert lr.rel_l2(lr.wgrad_ref(d, xb.store, xb.guard, gb.store, gb.guard)[0], want_dw) > 1e-3
+
+
+def test_checker_rejects_sabotaged_outputs():
+    """three ways a plan can be subtly wrong: one tap's weights dropped, one of 16 K ranges left out, one 16-pixel tile never written"""
+    x, w, xb, ob = _problem(77, 2, 8, 64, 32, 3, 1, 64, 32)
+    d = _conv_desc(xb, ob, 3, 1, 32)
+    wp = _packed(w)
+    R = lr.igemm_ref(d, xb.store, xb.guard, wp)
+
+    def launch(wflat):
+        wm = wflat.view(32, 3, 3, 64).permute(0, 3, 1, 2).float()
+        return _store(ob, F.conv2d(x.to(BF).float(), wm, padding=1).permute(0, 2, 3, 1))
+
+    good = launch(wp)
+    assert not R.check(good)[1]
+    no_tap = wp.clone().view(32, 9, 64)
+    no_tap[:, 4] = 0
+    assert R.check(launch(no_tap.reshape(-1)), what="tap")[1]
+    no_range = wp.clone().view(32, 16, 36)              # K = 576 in 16 ranges of 36
+    no_range[:, 11] = 0
+    assert R.check(launch(no_range.reshape(-1)), what="K range")[1]
+    old = torch.randn(ob.N * ob.img).to(BF)
+    stale = good.clone()
+    lr._out_view(stale, d)[0, 2:4] = lr._out_view(old, d)[0, 2:4]      # flattened output pixels 16 .. 31 keep what the buffer held before
+    fails = R.check(stale, what="tile")[1]
+    assert fails and "outside their bound" in fails[0]
