@@ -9,13 +9,18 @@ igemm_ref(...) evaluates every output element the descriptor addresses in fp64 f
     |got - ref| <= 2^-8 |ref| + 1.01 Ktot 2^-24 (|patch row| |weight row| + |bias| + |aux|) + 2^-126
 
 (one bf16 rounding plus the worst case of an fp32 sum of Ktot products, by Cauchy-Schwarz); a pooled element takes the largest bound of its window.
+
+Below them: BatchNorm forward / backward in training mode (bn.hip) and the pools (pool.hip) on logical NHWC fp64 views, each with a per-element
+bound derived from the kernel's arithmetic (check_values compares any region against such a reference).
 """
 
 from __future__ import annotations
 
 import math
+from types import SimpleNamespace
 
 import torch
+import torch.nn.functional as F
 
 EPI_NONE, EPI_BIAS, EPI_BIAS_LRELU, EPI_MUL_DLRELU, EPI_BIAS_ADD_LRELU = 0, 1, 2, 3, 4
 CHUNK_BYTES = 256 << 20       # fp64 im2col rows per matmul (the patches of one image at least)
@@ -35,6 +40,8 @@ def igemm_extent(d, what: str):
               + ((Wo - 1) * s + KW - 1) * _g(d, "in_px_stride") + T)
         return lo, hi
     if what == "w":
+        if _g(d, "w_blocked"):
+            return 0, (_g(d, "Cout") + 127) // 128 * 128 * KH * KW * T
         return 0, _g(d, "Cout") * KH * KW * T
     if what == "out":
         return 0, N * _g(d, "out_img_stride")
@@ -142,7 +149,7 @@ def igemm_ref(d, inp, in_base, w, bias=None, aux=None, aux_base=0, images=None, 
         R.aux_ref = torch.full_like(R.aux_addressed, math.nan, dtype=torch.float64)
         R.aux_bnd = torch.full_like(R.aux_addressed, -1.0, dtype=torch.float64)
         _aux_view(R.aux_addressed, d).fill_(True)
-    wm = w.as_strided((Co, K), (K, 1), w.storage_offset()).to(dev, torch.float64)
+    wm = weight_matrix(w, Co, K, bool(_g(d, "w_blocked"))).to(dev, torch.float64)
     wn = wm.norm(dim=1)
     b = bias.to(dev, torch.float64)[:Co] if (bias is not None and epi in (EPI_BIAS, EPI_BIAS_LRELU, EPI_BIAS_ADD_LRELU)) else None
     imgs = list(range(N)) if images is None else sorted(set(int(i) for i in images if i < N))
@@ -264,3 +271,149 @@ def wgrad_ref(d, x, x_base, dy, dy_base=0, device=None):
 def rel_l2(got, ref) -> float:
     got, ref = got.double().reshape(-1), ref.double().reshape(-1)
     return float((got - ref).norm() / ref.norm().clamp_min(1e-300))
+
+
+def weight_matrix(w, Co, K, blocked=False):
+    """[Cout][K] view of a forward weight operand: row-major, or (blocked, yolo_igemm_desc.w_blocked = 1) the Linear panels
+    [ceil(Cout/128)][K/64][128][64] of yolo_pack_fc_weight_blocked"""
+    if not blocked:
+        return w.as_strided((Co, K), (K, 1), w.storage_offset())
+    nb = (Co + 127) // 128
+    panels = w.as_strided((nb, 128, K // 64, 64), (128 * K, 64, 128 * 64, 1), w.storage_offset())
+    return panels.reshape(nb * 128, K)[:Co]
+
+
+# ---- element-wise check of any launch ------------------------------------------------------------------------------------------------------------
+
+U = 2.0 ** -24          # unit roundoff of fp32
+
+
+def check_values(ref, bnd, got, tag, fails, what=""):
+    """ref / bnd fp64 over a region, got the region as stored: bnd < 0 not checked, bnd == 0 equal to ref (ref is then the value as stored),
+    else |got - ref| <= bnd.  Appends a message to `fails` on a violation; -> worst |err| / bound (0 for exact elements)"""
+    m = (bnd >= 0).reshape(-1)
+    if not bool(m.any()):
+        return 0.0
+    g = got.reshape(-1)[: m.numel()].double()[m]
+    r, b = ref.reshape(-1)[m], bnd.reshape(-1)[m]
+    err = (g - r).abs()
+    ratio = torch.where(b > 0, err / b.clamp_min(TINY), torch.where(err == 0, torch.zeros_like(err), torch.full_like(err, math.inf)))
+    ratio = torch.where(torch.isfinite(g), ratio, torch.full_like(ratio, math.inf))
+    worst = float(ratio.max())
+    if worst > 1.0:
+        i = int(ratio.argmax())
+        fails.append(f"{what}: {int((ratio > 1.0).sum())} of {int(m.sum())} {tag} elements outside their bound (element {int(torch.nonzero(m).flatten()[i])}: "
+                     f"got {float(g[i]):.6g}, ref {float(r[i]):.6g}, bound {float(b[i]):.3g})")
+    return worst
+
+
+# ---- BatchNorm in training mode (bn.hip) ---------------------------------------------------------------------------------------------------------
+
+def bn_lane_pixels(P, C):
+    """pixels each lane of bn.hip's statistics / backward-reduction launch adds in fp32: groups of 8 channels, 256 // min(C/8, 256) pixel lanes per
+    workgroup, ~32 pixels per lane, at most 2048 workgroups along the pixels (the launch's own grid formula)"""
+    gpb = min(C // 8, 256)
+    ppb = 256 // gpb
+    gy = min(2048, max(1, -(-P // (ppb * 32))))
+    return -(-P // (gy * ppb))
+
+
+def bn_stats_ref(z, L):
+    """z fp64 [P][C] -> (mean, biased variance, bound of the kernel's mean, bound of its variance) when each lane adds L values and L squares in fp32
+    and the lanes' sums meet in fp64: var = E[z^2] - mean^2 then carries (L + 2) u E[z^2], so |mean| / std of a channel sets its error"""
+    P = z.shape[0]
+    mean = z.mean(0)
+    var = ((z - mean) ** 2).mean(0)
+    sq = (z * z).sum(0) / P
+    dm = 1.01 * (L + 1) * U * z.abs().sum(0) / P
+    dv = 1.01 * (L + 2) * U * sq + 2.0 * mean.abs() * dm + dm * dm + 2.0 ** -50 * sq
+    return mean, var, dm, dv
+
+
+def bn_fwd_ref(z, mean, var, dm, dv, gamma, beta, eps, residual=None, relu=False):
+    """bn_finalize + bn_apply from fp64 statistics (mean, var) whose kernel values lie within (dm, dv):
+    y = [relu](fma(z, scale, shift) [+ residual]) in fp32, scale = fp32(gamma invstd), shift = fp32(beta - mean scale), one bf16 rounding.
+    The statistics' errors enter as (z - mean) dscale + dmean scale (shift is formed from the kernel's own mean and scale); the fp32 roundings of
+    scale, shift, the fma and the residual add come on top.  -> namespace: y, bnd [P][C]; save, save_bnd [4][C] (mean, invstd, scale, shift)"""
+    g, b = gamma.double(), beta.double()
+    v = var.clamp_min(0.0)
+    inv = (v + eps).rsqrt()
+    dinv = torch.maximum(((v - dv).clamp_min(0.0) + eps).rsqrt() - inv, inv - (v + dv + eps).rsqrt())
+    scale = g * inv
+    dscale = g.abs() * dinv
+    shift = b - mean * scale
+    t = z * scale + shift
+    err = (z - mean).abs() * dscale + dm * (scale.abs() + dscale) + U * (z.abs() * scale.abs() + shift.abs() + t.abs())
+    if residual is not None:
+        t = t + residual
+        err = err + U * t.abs()
+    if relu:
+        t = t.clamp_min(0.0)
+    R = SimpleNamespace(y=t, bnd=(1 + 2.0 ** -8) * 1.01 * err + 2.0 ** -8 * t.abs() + TINY)
+    R.save = torch.stack([mean, inv, scale, shift])
+    R.save_bnd = 1.01 * torch.stack([dm + U * mean.abs(), dinv + U * inv, dscale + U * scale.abs(),
+                                     dm * (scale.abs() + dscale) + mean.abs() * dscale + U * shift.abs()]) + TINY
+    return R
+
+
+def bn_running_ref(rm, rv, mean, var, dm, dv, momentum, P):
+    """running_mean / running_var after one update (unbiased variance, as aten) and their bounds"""
+    unb = P / (P - 1) if P > 1 else 1.0
+    new_m = (1.0 - momentum) * rm.double() + momentum * mean
+    new_v = (1.0 - momentum) * rv.double() + momentum * var * unb
+    return new_m, momentum * dm + 2.02 * U * new_m.abs() + TINY, new_v, momentum * dv * unb + 2.02 * U * new_v.abs() + TINY
+
+
+def bn_bwd_ref(dy, z, gamma, save, L, mask=None, frozen=False):
+    """bn_bwd_reduce / finalize / apply of one launch from its operands: dy, z fp64 [P][C]; mask bool [P][C] or None; save the forward's fp32 [4][C]
+    (mean, invstd, scale, shift).  dy' = dy mask; dbeta = sum dy', dgamma = sum dy' xhat (lanes of L pixels in fp32, fp64 after);
+    dz = gamma invstd (dy' - dbeta / P - xhat dgamma / P) in fp32 (frozen: gamma invstd dy'), one bf16 rounding"""
+    P = z.shape[0]
+    mean, inv = save[0].double(), save[1].double()
+    g = dy if mask is None else torch.where(mask, dy, torch.zeros_like(dy))
+    xh = (z - mean) * inv
+    gx = g * xh
+    s1, s2 = g.sum(0), gx.sum(0)
+    e1 = 1.01 * (L + 1) * U * g.abs().sum(0)
+    e2 = 1.01 * (L + 4) * U * gx.abs().sum(0)
+    c0 = gamma.double() * inv
+    if frozen:
+        c1 = c2 = d1 = d2 = torch.zeros_like(s1)
+    else:
+        c1, c2 = s1 / P, s2 / P
+        d1, d2 = e1 / P + U * c1.abs(), e2 / P + U * c2.abs()
+    inner = g - c1 - xh * c2
+    mag = g.abs() + c1.abs() + (xh * c2).abs()
+    dinner = d1 + xh.abs() * d2 + 2.02 * U * xh.abs() * c2.abs() + 3.03 * U * mag
+    dz = c0 * inner
+    err = c0.abs() * (dinner + 2.02 * U * mag)
+    R = SimpleNamespace(g=g, dz=dz, bnd=(1 + 2.0 ** -8) * 1.01 * err + 2.0 ** -8 * dz.abs() + TINY)
+    R.dbeta, R.dbeta_bnd = s1, e1 + U * s1.abs() + TINY
+    R.dgamma, R.dgamma_bnd = s2, e2 + U * s2.abs() + TINY
+    return R
+
+
+# ---- pools (pool.hip), NHWC fp64 views ----------------------------------------------------------------------------------------------------------
+
+def maxpool2_ref(x):
+    """MaxPool2d(2, 2) of x [N][H][W][C] (exact)"""
+    N, H, W, C = x.shape
+    return x[:, : H // 2 * 2, : W // 2 * 2].reshape(N, H // 2, 2, W // 2, 2, C).amax((2, 4))
+
+
+def maxpool3s2_ref(x):
+    """MaxPool2d(3, stride 2, pad 1) of x [N][H][W][C] (exact; -inf padding, as the operator)"""
+    return F.max_pool2d(x.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
+
+
+def maxpool3s2_bwd_ref(x, dy):
+    """aten's MaxPool2d(3, 2, 1) backward: each window's dy goes to its FIRST maximum in row-major order; a pixel sums <= 4 windows in fp32, one bf16
+    rounding.  x [N][H][W][C], dy [N][Ho][Wo][C] fp64 -> (dx, bound) [N][H][W][C]"""
+    N, H, W, C = x.shape
+    _, idx = F.max_pool2d(x.permute(0, 3, 1, 2).contiguous(), 3, 2, 1, return_indices=True)
+    idx = idx.reshape(N, C, -1)
+    g = dy.permute(0, 3, 1, 2).reshape(N, C, -1)
+    dx = torch.zeros(N, C, H * W, dtype=torch.float64, device=x.device).scatter_add_(2, idx, g)
+    ab = torch.zeros_like(dx).scatter_add_(2, idx, g.abs())
+    dx, ab = (t.view(N, C, H, W).permute(0, 2, 3, 1) for t in (dx, ab))
+    return dx, 2.0 ** -8 * dx.abs() + 3.03 * U * ab + TINY

@@ -78,6 +78,73 @@ def test_batchnorm_backward_matches_autograd(relu, stride, from_z, frozen):
     assert torch.equal(ga.interior().float().cpu().permute(0, 3, 1, 2), _bf(dy * mask)) or _rel(ga.interior().permute(0, 3, 1, 2), dy * mask) < 0.003
 
 
+# (N, H, W, C, |mean| / std, relu, residual): the grid of bn.hip's reductions (pixel lanes per workgroup = 256 // min(C/8, 256), ~32 pixels per lane,
+# at most 2048 workgroups along the pixels) at its edges
+BN_EDGES = [(1, 3, 5, 64, 1.0, True, False),          # 15 pixels: fewer than the 32 pixel lanes of one workgroup
+            (64, 7, 7, 2048, 1.0, True, False),       # one lane per workgroup, grid stride 98 > a 7x7 map (PixIter's image step sn > 0)
+            (64, 7, 7, 64, 10.0, False, False),       # grid stride 128 > 49
+            (2, 185, 187, 2048, 1.0, True, True),     # odd 185 x 187 map, 2048 workgroups (the cap), 34 pixels per lane: unrolled rounds + a tail
+            (8, 28, 28, 256, 1.0, True, False), (8, 28, 28, 256, 10.0, True, False), (8, 28, 28, 256, 30.0, True, True),
+            (2, 185, 187, 2048, 30.0, True, False)]
+
+
+@pytest.mark.parametrize("N,H,W,C,ratio,relu,res", BN_EDGES)
+def test_batchnorm_launches_within_fp64_bounds(N, H, W, C, ratio, relu, res):
+    """one forward (batch statistics, running statistics, save_mean_invstd, output into a second buffer) and one backward (ReLU mask from y, masked dy
+    stored back) against launch_ref's fp64 references, element by element within bounds derived from the kernels' arithmetic"""
+    import launch_ref as lr
+    from yolo import engine
+    from yolo._hip import BN_ACC_REPLICAS, check, lib, ptr, stream
+    dev = torch.device("cuda")
+    g = torch.Generator(device=dev).manual_seed(N * C + int(ratio))
+    P = N * H * W
+    std = torch.rand(C, device=dev, generator=g) + 0.5
+    sign = torch.where(torch.rand(C, device=dev, generator=g) < 0.5, -1.0, 1.0)
+    za, ya, ra, ga, dz = (engine.Act(N, H, W, C, 1, dev) for _ in range(5))
+    za.interior().copy_((sign * ratio * std + std * torch.randn(N, H, W, C, device=dev, generator=g)).to(torch.bfloat16))
+    ra.interior().copy_(torch.randn(N, H, W, C, device=dev, generator=g).to(torch.bfloat16))
+    gamma, beta = torch.rand(C, device=dev, generator=g) + 0.5, torch.randn(C, device=dev, generator=g) * 0.5
+    rm0, rv0 = torch.randn(C, device=dev, generator=g) * 0.1, torch.rand(C, device=dev, generator=g) + 0.5
+    rm, rv = rm0.clone(), rv0.clone()
+    acc = torch.zeros(BN_ACC_REPLICAS * 2 * C, dtype=torch.float64, device=dev)
+    ss, save = torch.empty(2 * C, device=dev), torch.full((4 * C,), float("nan"), device=dev)
+    ya.interior().fill_(float("nan"))
+    st = stream()
+    check(lib().yolo_batchnorm_train_fwd(za.p, N, H, W, C, 1, ptr(gamma), ptr(beta), 1e-5, 0.1, ptr(rm), ptr(rv), ra.p if res else None, 1,
+                                         1 if relu else 0, ptr(acc), ptr(ss), ya.p, 1, ptr(save), 0, st))
+    torch.cuda.synchronize()
+    assert float(acc.abs().max()) == 0.0
+    zz = za.interior().double().reshape(P, C)
+    L = lr.bn_lane_pixels(P, C)
+    mean, var, dm, dv = lr.bn_stats_ref(zz, L)
+    R = lr.bn_fwd_ref(zz, mean, var, dm, dv, gamma, beta, 1e-5, ra.interior().double().reshape(P, C) if res else None, relu)
+    fails, worst = [], {}
+    tag = f"N {N} {H}x{W} C {C} |mean|/std {ratio}"
+    worst["y"] = lr.check_values(R.y, R.bnd, ya.interior().reshape(P, C), "y", fails, tag)
+    worst["save"] = lr.check_values(R.save.reshape(-1), R.save_bnd.reshape(-1), save, "save_mean_invstd", fails, tag)
+    new_m, bm, new_v, bv = lr.bn_running_ref(rm0, rv0, mean, var, dm, dv, 0.1, P)
+    worst["running"] = max(lr.check_values(new_m, bm, rm, "running_mean", fails, tag), lr.check_values(new_v, bv, rv, "running_var", fails, tag))
+    assert float(ya.view()[:, 0].abs().max()) == 0.0 and float(ya.view()[:, :, -1].abs().max()) == 0.0          # halo untouched
+    # backward
+    ga.interior().copy_(torch.randn(N, H, W, C, device=dev, generator=g).to(torch.bfloat16))
+    dy0 = ga.interior().double().reshape(P, C)
+    dz.interior().fill_(float("nan"))
+    dgam, dbet = torch.full((C,), float("nan"), device=dev), torch.full((C,), float("nan"), device=dev)
+    coef = torch.empty(3 * C, device=dev)
+    check(lib().yolo_batchnorm_bwd(ga.p, 1, ya.p if relu else None, 1, za.p, 1, N, H, W, C, ptr(gamma), ptr(save), dz.p, dz.img_stride, dz.row_stride,
+                                   dz.px_stride, dz.interior_off(), 1, 0, ptr(dgam), ptr(dbet), ptr(acc), ptr(coef), st))
+    torch.cuda.synchronize()
+    assert float(acc.abs().max()) == 0.0
+    B = lr.bn_bwd_ref(dy0, zz, gamma, save.view(4, C), L, ya.interior().reshape(P, C) > 0 if relu else None)
+    worst["dz"] = lr.check_values(B.dz, B.bnd, dz.interior().reshape(P, C), "dz", fails, tag)
+    worst["dgamma"] = lr.check_values(B.dgamma, B.dgamma_bnd, dgam, "dgamma", fails, tag)
+    worst["dbeta"] = lr.check_values(B.dbeta, B.dbeta_bnd, dbet, "dbeta", fails, tag)
+    worst["masked dy"] = lr.check_values(B.g, torch.zeros_like(B.g), ga.interior().reshape(P, C), "masked dy", fails, tag)
+    assert float(dz.view()[:, 0].abs().max()) == 0.0 and float(dz.view()[:, :, -1].abs().max()) == 0.0
+    print(f"\n{tag}: worst |err| / bound " + "  ".join(f"{k} {v:.3g}" for k, v in worst.items()), flush=True)
+    assert not fails, "\n".join(fails)
+
+
 @pytest.mark.parametrize("H,W", [(16, 20), (15, 19), (7, 8)])
 def test_maxpool3s2_backward_matches_autograd(H, W):
     from yolo import engine

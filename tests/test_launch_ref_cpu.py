@@ -256,3 +256,165 @@ def test_checker_rejects_sabotaged_outputs():
     lr._out_view(stale, d)[0, 2:4] = lr._out_view(old, d)[0, 2:4]      # flattened output pixels 16 .. 31 keep what the buffer held before
     fails = R.check(stale, what="tile")[1]
     assert fails and "outside their bound" in fails[0]
+
+
+def test_blocked_weight_panels_are_the_linear_weight():
+    """w_blocked = 1: the [ceil(O/128)][K/64][128][64] panels of yolo_pack_fc_weight_blocked (rows >= O zero) describe the same Linear layer"""
+    g = torch.Generator().manual_seed(8)
+    O, K, N = 200, 192, 3
+    w = torch.randn(O, K, generator=g)
+    x = torch.randn(N, K, generator=g)
+    panels = torch.zeros(2, K // 64, 128, 64)
+    wp = torch.zeros(256, K)
+    wp[:O] = w
+    panels[:] = wp.view(2, 128, K // 64, 64).permute(0, 2, 1, 3)
+    d = _desc(N=N, Ho=1, Wo=1, in_img_stride=K, in_row_stride=0, in_px_stride=K, in_off=0, stride=1, KH=1, KW=1, tap_len=K, Cout=O,
+              out_img_stride=O, out_row_stride=0, out_px_stride=O, out_off=0, out_fp32=1, w_blocked=1)
+    assert lr.igemm_extent(d, "w") == (0, panels.numel())
+    R = lr.igemm_ref(d, x.to(BF).reshape(-1), 0, panels.to(BF).reshape(-1))
+    assert torch.allclose(R.ref, F.linear(_bf(x), _bf(w)).reshape(-1), rtol=1e-12, atol=1e-12)
+    d.w_blocked = 0
+    assert lr.igemm_extent(d, "w") == (0, O * K)
+    assert torch.equal(lr.igemm_ref(d, x.to(BF).reshape(-1), 0, w.to(BF).reshape(-1)).ref, R.ref)
+
+
+def _bn_problem(seed, N, H, W, C, ratio):
+    """bf16 conv outputs whose channels have |mean| / std = ratio"""
+    g = torch.Generator().manual_seed(seed)
+    std = torch.rand(C, generator=g) + 0.5
+    sign = torch.where(torch.rand(C, generator=g) < 0.5, -1.0, 1.0)
+    z = _bf(sign * ratio * std + std * torch.randn(N, H, W, C, generator=g))
+    return z, (torch.rand(C, generator=g) + 0.5).double(), torch.randn(C, generator=g).double() * 0.5, g
+
+
+def _bn_kernel_fwd(z, gamma, beta, eps, L, residual=None, relu=False, lanes_dropped=0):
+    """bn.hip's forward arithmetic on the CPU: fp32 lane partials of L pixels, fp64 across lanes, fp32 scale / shift, fma, bf16 store
+    (lanes_dropped: the last lanes' partials lost, as a wrong grid stride would)"""
+    P, C = z.shape
+    zf = z.float()
+    nl = -(-P // L)
+    pad = torch.zeros(nl * L - P, C)
+    lanes = torch.cat([zf, pad]).view(nl, L, C)
+    s1 = torch.zeros(nl, C, dtype=torch.float32)
+    s2 = torch.zeros(nl, C, dtype=torch.float32)
+    for i in range(L):
+        s1 += lanes[:, i]
+        s2 += lanes[:, i] * lanes[:, i]
+    s1, s2 = s1[: nl - lanes_dropped].double().sum(0), s2[: nl - lanes_dropped].double().sum(0)
+    mean = s1 / P
+    var = (s2 / P - mean * mean).clamp_min(0)
+    sc = gamma * (var + eps).rsqrt()
+    scale, shift = sc.float(), (beta - mean * sc).float()
+    y = (zf.double() * scale.double() + shift.double()).float()      # fma: one rounding of the exact product + sum
+    if residual is not None:
+        y = y + residual.float()
+    if relu:
+        y = y.clamp_min(0)
+    return y.to(BF).double(), torch.stack([mean, (var + eps).rsqrt(), scale.double(), shift.double()]).float()
+
+
+@pytest.mark.parametrize("ratio,relu,res", [(1.0, True, False), (10.0, False, True), (30.0, True, False)])
+def test_batchnorm_forward_reference_equals_torch(ratio, relu, res):
+    N, H, W, C = 2, 9, 11, 64
+    z, gamma, beta, g = _bn_problem(int(ratio) + relu, N, H, W, C, ratio)
+    r = _bf(torch.randn(N, H, W, C, generator=g)) if res else None
+    P = N * H * W
+    zz, rr = z.reshape(P, C), (r.reshape(P, C) if res else None)
+    L = lr.bn_lane_pixels(P, C)
+    assert L == 7                     # 198 pixels over 32 lanes
+    mean, var, dm, dv = lr.bn_stats_ref(zz, L)
+    R = lr.bn_fwd_ref(zz, mean, var, dm, dv, gamma, beta, 1e-5, rr, relu)
+    rm, rv = torch.randn(C, generator=g).double(), torch.rand(C, generator=g).double() + 0.5
+    rm_t, rv_t = rm.clone(), rv.clone()
+    want = F.batch_norm(z.permute(0, 3, 1, 2), rm_t, rv_t, gamma, beta, True, 0.1, 1e-5)
+    if res:
+        want = want + r.permute(0, 3, 1, 2)
+    if relu:
+        want = want.clamp_min(0)
+    assert torch.allclose(R.y, want.permute(0, 2, 3, 1).reshape(P, C), rtol=1e-10, atol=1e-10)
+    new_m, bm, new_v, bv = lr.bn_running_ref(rm, rv, mean, var, dm, dv, 0.1, P)
+    assert torch.allclose(new_m, rm_t, rtol=1e-12, atol=1e-12) and torch.allclose(new_v, rv_t, rtol=1e-12, atol=1e-12)
+    # the kernel's own arithmetic lies inside every bound; statistics one pixel lane short and a channel group left stale do not
+    y, save = _bn_kernel_fwd(zz, gamma, beta, 1e-5, L, rr, relu)
+    fails = []
+    assert lr.check_values(R.y, R.bnd, y, "y", fails) <= 1.0 and lr.check_values(R.save, R.save_bnd, save, "save", fails) <= 1.0, fails
+    short, _ = _bn_kernel_fwd(zz, gamma, beta, 1e-5, L, rr, relu, lanes_dropped=1)
+    assert lr.check_values(R.y, R.bnd, short, "y", fails) > 1.0
+    stale = y.clone()
+    stale[:, 16:24] = zz[:, 16:24]
+    assert lr.check_values(R.y, R.bnd, stale, "y", fails) > 1.0
+
+
+@pytest.mark.parametrize("mask_from,frozen", [("y", False), ("z", False), (None, False), ("y", True)])
+def test_batchnorm_backward_reference_equals_autograd(mask_from, frozen):
+    N, H, W, C = 2, 7, 9, 32
+    z, gamma, beta, g = _bn_problem(3 + frozen, N, H, W, C, 2.0)
+    P = N * H * W
+    dy = _bf(torch.randn(N, H, W, C, generator=g))
+    rm, rv = torch.randn(C, generator=g).double(), torch.rand(C, generator=g).double() + 0.5
+    zc = z.permute(0, 3, 1, 2).clone().requires_grad_(True)
+    gc, bc = gamma.clone().requires_grad_(True), beta.clone().requires_grad_(True)
+    y = F.batch_norm(zc, rm.clone(), rv.clone(), gc, bc, not frozen, 0.1, 1e-5)
+    if mask_from is not None:
+        y = y.clamp_min(0)
+    y.backward(dy.permute(0, 3, 1, 2))
+    zz = z.reshape(P, C)
+    if frozen:
+        mean, inv = rm, (rv + 1e-5).rsqrt()
+    else:
+        mean, inv = zz.mean(0), (zz.var(0, unbiased=False) + 1e-5).rsqrt()
+    save = torch.stack([mean, inv, gamma * inv, beta - mean * gamma * inv])
+    yv = y.detach().permute(0, 2, 3, 1).reshape(P, C)
+    mask = {"y": yv > 0, "z": zz * save[2] + save[3] > 0, None: None}[mask_from]
+    L = lr.bn_lane_pixels(P, C)
+    R = lr.bn_bwd_ref(dy.reshape(P, C), zz, gamma, save, L, mask, frozen)
+    assert torch.allclose(R.dz, zc.grad.permute(0, 2, 3, 1).reshape(P, C), rtol=1e-9, atol=1e-9)
+    assert torch.allclose(R.dgamma, gc.grad, rtol=1e-9, atol=1e-9) and torch.allclose(R.dbeta, bc.grad, rtol=1e-9, atol=1e-9)
+    # an fp32 evaluation in the kernel's order lies inside the bounds
+    gf, zf, sv = R.g.float(), zz.float(), save.float()
+    xh = (zf - sv[0]) * sv[1]
+    s1, s2 = gf.double().sum(0), (gf * xh).double().sum(0)
+    c0 = gamma.float() * sv[1]
+    c1, c2 = ((s1 / P).float(), (s2 / P).float()) if not frozen else (torch.zeros(C), torch.zeros(C))
+    dz = (c0 * (gf - c1 - xh * c2)).to(BF)
+    fails = []
+    assert lr.check_values(R.dz, R.bnd, dz, "dz", fails) <= 1.0, fails
+    assert lr.check_values(R.dbeta, R.dbeta_bnd, s1.float(), "dbeta", fails) <= 1.0, fails
+    assert lr.check_values(R.dgamma, R.dgamma_bnd, s2.float(), "dgamma", fails) <= 1.0, fails
+    if not frozen:      # the batch terms taken from half the pixels are rejected
+        c1h = (gf[: P // 2].double().sum(0) / (P // 2)).float()
+        assert lr.check_values(R.dz, R.bnd, (c0 * (gf - c1h - xh * c2)).to(BF), "dz", fails) > 1.0
+
+
+@pytest.mark.parametrize("H,W", [(8, 10), (7, 9)])
+def test_pool_references_equal_torch(H, W):
+    g = torch.Generator().manual_seed(H)
+    N, C = 2, 16
+    x = _bf(torch.relu(torch.randn(N, H, W, C, generator=g)))
+    x[:, 2:6, 3:7] = 0.0                     # ties: windows of equal values
+    xc = x.permute(0, 3, 1, 2).clone().requires_grad_(True)
+    y = F.max_pool2d(xc, 3, 2, 1)
+    assert torch.equal(lr.maxpool3s2_ref(x), y.detach().permute(0, 2, 3, 1))
+    assert torch.equal(lr.maxpool2_ref(x), F.max_pool2d(x.permute(0, 3, 1, 2), 2, 2).permute(0, 2, 3, 1))
+    dy = _bf(torch.randn(y.shape, generator=g))
+    y.backward(dy)
+    dx, bnd = lr.maxpool3s2_bwd_ref(x, dy.permute(0, 2, 3, 1))
+    want = xc.grad.permute(0, 2, 3, 1)
+    assert torch.allclose(dx, want, rtol=1e-12, atol=1e-12)
+    fails = []
+    assert lr.check_values(dx, bnd, want.float().to(BF), "dx", fails) <= 1.0, fails
+    # the gradient of a tied window routed to its LAST maximum is rejected
+    Ho, Wo = y.shape[2], y.shape[3]
+    last = torch.zeros_like(want)
+    for oy in range(Ho):
+        for ox in range(Wo):
+            win = x[:, max(2 * oy - 1, 0): 2 * oy + 2, max(2 * ox - 1, 0): 2 * ox + 2]           # [N][h][w][C]
+            flat = win.reshape(N, -1, C)
+            rev = flat.flip(1).argmax(1)                                                       # last maximum
+            k = flat.shape[1] - 1 - rev
+            wy, wx = k // win.shape[2] + max(2 * oy - 1, 0), k % win.shape[2] + max(2 * ox - 1, 0)
+            for n in range(N):
+                for c in range(C):
+                    last[n, wy[n, c], wx[n, c], c] += dy[n, c, oy, ox]
+    assert not torch.equal(last, want)
+    assert lr.check_values(dx, bnd, last, "dx", fails) > 1.0
