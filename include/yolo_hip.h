@@ -523,6 +523,46 @@ int yolo_preprocess_u8(const unsigned char *src_u8, int N, int Hs, int Ws, int H
                        unsigned char *tmp_u8, const float *mean3, const float *std3, void *out_nhwc4_bf16, int halo,
                        float *out_nchw, yolo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Training / validation input path on the device.  Replaces the per-sample host transforms of the reference
+ * (src/yolo/dataset.py:288-319 RandomResizedCrop + ColorJitter, 325-409 __getitem__'s transform calls): the host decodes
+ * the file and draws the random parameters; crop -> Resize (Pillow BILINEAR, bit-exact) -> ColorJitter operations in the
+ * sampled order (Pillow's ImageEnhance.Brightness / ImageEnhance.Color and an H-byte shift through its HSV conversion,
+ * bit-exact) -> ToTensor -> Normalize run here for a whole batch of images of DIFFERENT sizes.
+ * One descriptor per image; the images lie packed in one uint8 buffer (HWC RGB). */
+typedef struct yolo_augment_desc {
+    int64_t src_off;            /* byte offset of the image in the packed buffer */
+    int64_t tmp_off;            /* byte offset of its [ch][Wo][3] slice in tmp_u8 (used when cw != Wo) */
+    int32_t Hs, Ws;             /* decoded size */
+    int32_t top, left, ch, cw;  /* crop (the whole image for validation) */
+    /* Pillow's tables for cw -> Wo and ch -> Ho in DEVICE memory: int32 [out][2 + k] rows of (first input index, count,
+       k 22-bit fixed-point weights); NULL / k = 0 for an axis whose size does not change */
+    const int32_t *htab;
+    const int32_t *vtab;
+    int32_t hk, vk;
+    int32_t n_ops;              /* 0..3 colour operations, applied in the order of ops[] */
+    int32_t ops[3];             /* YOLO_AUG_BRIGHTNESS / _SATURATION / _HUE */
+    float brightness;           /* ImageEnhance.Brightness factor */
+    float saturation;           /* ImageEnhance.Color factor */
+    int32_t hue_shift;          /* int(delta * 255), added to the H byte modulo 256 */
+    int32_t reserved;
+} yolo_augment_desc;
+#define YOLO_AUG_BRIGHTNESS 0
+#define YOLO_AUG_SATURATION 1
+#define YOLO_AUG_HUE 2
+
+/* descs_host is validated before any HIP call (crop inside its image and inside src_bytes, tables present where a size
+ * changes, tmp slice inside tmp_bytes, n_ops <= 3, known operations); descs_dev is the same array in device memory, which
+ * the kernels read.  Two launches for the whole batch: a horizontal pass over the crop rows of every image that needs
+ * one into tmp_u8, then a vertical pass that finishes each output pixel in registers.  mean3 / std3 are HOST pointers.
+ * Outputs (each may be NULL, not all): out_nhwc4 = zero-haloed NHWC4 bf16 [N][Ho+2h][Wo+2h][4] (interior written, channel
+ * 3 = 0, exactly as yolo_preprocess_u8 leaves it), out_nchw = fp32 [N][3][Ho][Wo], out_u8 = the augmented image
+ * [N][Ho][Wo][3] before ToTensor. */
+int yolo_augment_u8(const unsigned char *src_u8, int64_t src_bytes, const yolo_augment_desc *descs_host,
+                    const yolo_augment_desc *descs_dev, int N, int Ho, int Wo, unsigned char *tmp_u8, int64_t tmp_bytes,
+                    const float *mean3, const float *std3, void *out_nhwc4_bf16, int halo, float *out_nchw,
+                    unsigned char *out_u8, yolo_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

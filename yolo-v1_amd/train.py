@@ -48,6 +48,9 @@ def main():
     ap.add_argument("--checkpoint-dir", default="checkpoints")
     ap.add_argument("--resume", default=None)
     ap.add_argument("--synthetic", type=int, default=0, help="train on N synthetic images (no dataset needed)")
+    ap.add_argument("--device-augment", action="store_true",
+                    help="VOC only: loaders ship decoded uint8 images + sampled parameters, crop / resize / colour jitter / normalise run on the device")
+    ap.add_argument("--voc-root", default=None, help="dataset root (default: $VOC_ROOT or ./data)")
     a = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -62,12 +65,19 @@ def main():
     if a.synthetic:
         train_ds, val_ds = SyntheticYOLODataset(a.synthetic, seed=0), SyntheticYOLODataset(max(a.batch_size, a.synthetic // 8), seed=1)
     else:
-        train_ds = create_voc_datasets([("2007", "trainval"), ("2012", "train")], augment=True)     # the reference's splits (src/train.py:106-122)
-        val_ds = create_voc_datasets([("2012", "val")], augment=False)
+        train_ds = create_voc_datasets([("2007", "trainval"), ("2012", "train")], augment=True, root=a.voc_root,
+                                       device_transform=a.device_augment)     # the reference's splits (src/train.py:106-122)
+        val_ds = create_voc_datasets([("2012", "val")], augment=False, root=a.voc_root, device_transform=a.device_augment)
+    collate = None
+    if a.device_augment:
+        if a.synthetic:
+            ap.error("--device-augment needs the VOC datasets (synthetic samples are fp32 tensors already)")
+        from yolo.augment import collate_u8
+        collate = collate_u8
     sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank) if world > 1 else None
     train_loader = DataLoader(train_ds, batch_size=a.batch_size, shuffle=sampler is None, sampler=sampler, num_workers=a.num_workers,
-                              pin_memory=device == "cuda", drop_last=True)
-    val_loader = DataLoader(val_ds, batch_size=a.batch_size, shuffle=False, num_workers=a.num_workers, pin_memory=device == "cuda")
+                              pin_memory=device == "cuda", drop_last=True, collate_fn=collate)
+    val_loader = DataLoader(val_ds, batch_size=a.batch_size, shuffle=False, num_workers=a.num_workers, pin_memory=device == "cuda", collate_fn=collate)
 
     backbone = YOLOv1Backbone() if a.backbone == "yolov1" else ResNetBackbone(pretrained=not a.no_pretrained, freeze=a.freeze_backbone)
     model = YOLOv1(backbone=backbone, num_classes=20, S=7, B=2).to(device)

@@ -89,6 +89,19 @@ class ConvUnpackItem(ctypes.Structure):
     _fields_ = [("dwp", c_void_p), ("dw", c_void_p), ("Cout", c_int), ("Cin", c_int), ("KH", c_int), ("KW", c_int)]
 
 
+class AugmentDesc(ctypes.Structure):
+    """struct yolo_augment_desc (include/yolo_hip.h): one image of a ragged uint8 batch."""
+
+    _fields_ = [("src_off", ctypes.c_int64), ("tmp_off", ctypes.c_int64),
+                ("Hs", ctypes.c_int32), ("Ws", ctypes.c_int32),
+                ("top", ctypes.c_int32), ("left", ctypes.c_int32), ("ch", ctypes.c_int32), ("cw", ctypes.c_int32),
+                ("htab", c_void_p), ("vtab", c_void_p),
+                ("hk", ctypes.c_int32), ("vk", ctypes.c_int32),
+                ("n_ops", ctypes.c_int32), ("ops", ctypes.c_int32 * 3),
+                ("brightness", ctypes.c_float), ("saturation", ctypes.c_float), ("hue_shift", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+AUG_BRIGHTNESS, AUG_SATURATION, AUG_HUE = 0, 1, 2      # YOLO_AUG_* (include/yolo_hip.h)
 EPI_NONE, EPI_BIAS, EPI_BIAS_LRELU, EPI_MUL_DLRELU, EPI_BIAS_ADD_LRELU = 0, 1, 2, 3, 4
 NMS_INFERENCE, NMS_METRICS = 0, 1
 
@@ -145,6 +158,8 @@ _SIGS = {
     "yolo_cast_bf16_to_f32": [c_void_p, c_long, c_void_p, c_void_p],
     "yolo_preprocess_u8": [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p,
                            ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p, c_int, c_void_p, c_void_p],
+    "yolo_augment_u8": [c_void_p, ctypes.c_int64, ctypes.POINTER(AugmentDesc), c_void_p, c_int, c_int, c_int, c_void_p, ctypes.c_int64,
+                        ctypes.POINTER(c_float), ctypes.POINTER(c_float), c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     "yolo_sumsq_f32": [c_void_p, c_long, c_void_p, c_void_p],
     "yolo_adam_step": [c_void_p, c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_float, c_float, c_long, c_void_p, c_float, c_void_p, c_void_p],
     "yolo_clip_scale_f32": [c_void_p, c_long, c_void_p, c_float, c_void_p],

@@ -47,8 +47,16 @@ class ResNetTrainFunction(torch.autograd.Function):
         return (None, None, None) + tuple(grads.get(p) if p.requires_grad else None for p in ctx.params)
 
 
+def run_plan(plan: Plan, x, drop_training: bool) -> torch.Tensor:
+    """x: NCHW fp32 device tensor, or a ``yolo.augment.U8Batch`` on the device (which never asks for an input gradient)"""
+    if not isinstance(x, torch.Tensor):
+        with torch.cuda.device(x.device):          # device_guard looks at tensor arguments only
+            return _run_plan(plan, x, drop_training)
+    return _run_plan(plan, x, drop_training)
+
+
 @_hip.device_guard
-def run_plan(plan: Plan, x: torch.Tensor, drop_training: bool) -> torch.Tensor:
+def _run_plan(plan: Plan, x, drop_training: bool) -> torch.Tensor:
     _hip.require_cuda(x)
     # grad mode must be sampled here: inside Function.forward it is always off
     need = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in plan.params))

@@ -23,7 +23,7 @@ import math
 import os
 import xml.etree.ElementTree as ET
 from pathlib import Path
-from typing import List, Tuple
+from typing import List, NamedTuple, Tuple
 
 import numpy as np
 import torch
@@ -89,6 +89,34 @@ def parse_voc_xml(node: ET.Element) -> dict:
     return {node.tag: inner}
 
 
+OP_BRIGHTNESS, OP_SATURATION, OP_HUE = 0, 1, 2      # = YOLO_AUG_* of include/yolo_hip.h
+
+
+class AugParams(NamedTuple):
+    """What ``_Augment.sample`` draws for one image: the crop, the colour operations in the order they are applied, their factors
+    (``hue`` is the fraction of the hue circle; the H byte moves by ``int(hue * 255)``).  The host path (``_Augment.apply``) and
+    the device path (yolo/augment.py -> yolo_augment_u8) both take it."""
+    top: int
+    left: int
+    ch: int
+    cw: int
+    ops: Tuple[int, ...] = ()
+    brightness: float = 1.0
+    saturation: float = 1.0
+    hue: float = 0.0
+
+
+def crop_boxes(boxes, p: AugParams, size) -> List[List[float]]:
+    """pixel-space XYXY boxes shifted into the crop, clamped to it and scaled with it to ``size`` = (H, W)"""
+    sx, sy = size[1] / p.cw, size[0] / p.ch
+    out = []
+    for x0, y0, x1, y1 in boxes:
+        x0, x1 = min(max(x0 - p.left, 0.0), p.cw) * sx, min(max(x1 - p.left, 0.0), p.cw) * sx
+        y0, y1 = min(max(y0 - p.top, 0.0), p.ch) * sy, min(max(y1 - p.top, 0.0), p.ch) * sy
+        out.append([x0, y0, x1, y1])
+    return out
+
+
 def _uniform(a: float, b: float) -> float:
     return float(torch.empty(1).uniform_(a, b).item())
 
@@ -129,29 +157,37 @@ class _Augment:
         hsv[..., 0] = (hsv[..., 0].astype(np.int16) + int(delta * 255)) % 256
         return Image.fromarray(hsv, "HSV").convert("RGB")
 
-    def __call__(self, image: Image.Image, boxes: List[List[float]]):
-        w, h = image.size
+    def sample(self, w: int, h: int) -> AugParams:
+        """Draw the parameters for a w x h image from torch's global generator: crop tries, brightness, saturation, hue,
+        then the order of the colour operations."""
         top, left, ch, cw = self._crop_params(w, h)
-        image = image.crop((left, top, left + cw, top + ch)).resize((self.size[1], self.size[0]), Image.BILINEAR)
-        sx, sy = self.size[1] / cw, self.size[0] / ch
-        out = []
-        for x0, y0, x1, y1 in boxes:
-            x0, x1 = min(max(x0 - left, 0.0), cw) * sx, min(max(x1 - left, 0.0), cw) * sx
-            y0, y1 = min(max(y0 - top, 0.0), ch) * sy, min(max(y1 - top, 0.0), ch) * sy
-            out.append([x0, y0, x1, y1])
-        ops = []
+        ops, b, s, hu = [], 1.0, 1.0, 0.0
         if self.brightness:
-            f = _uniform(max(0.0, 1 - self.brightness), 1 + self.brightness)
-            ops.append(lambda im, f=f: ImageEnhance.Brightness(im).enhance(f))
+            b = _uniform(max(0.0, 1 - self.brightness), 1 + self.brightness)
+            ops.append(OP_BRIGHTNESS)
         if self.saturation:
-            f = _uniform(max(0.0, 1 - self.saturation), 1 + self.saturation)
-            ops.append(lambda im, f=f: ImageEnhance.Color(im).enhance(f))
+            s = _uniform(max(0.0, 1 - self.saturation), 1 + self.saturation)
+            ops.append(OP_SATURATION)
         if self.hue:
-            f = _uniform(-self.hue, self.hue)
-            ops.append(lambda im, f=f: self._hue(im, f))
-        for k in torch.randperm(len(ops)).tolist():
-            image = ops[k](image)
-        return image, out
+            hu = _uniform(-self.hue, self.hue)
+            ops.append(OP_HUE)
+        order = tuple(ops[k] for k in torch.randperm(len(ops)).tolist())
+        return AugParams(top, left, ch, cw, order, b, s, hu)
+
+    def apply(self, image: Image.Image, boxes: List[List[float]], p: AugParams):
+        """The host path: crop, PIL bilinear resize and the colour operations of ``p`` in its order; boxes go with the crop."""
+        image = image.crop((p.left, p.top, p.left + p.cw, p.top + p.ch)).resize((self.size[1], self.size[0]), Image.BILINEAR)
+        for op in p.ops:
+            if op == OP_BRIGHTNESS:
+                image = ImageEnhance.Brightness(image).enhance(p.brightness)
+            elif op == OP_SATURATION:
+                image = ImageEnhance.Color(image).enhance(p.saturation)
+            else:
+                image = self._hue(image, p.hue)
+        return image, crop_boxes(boxes, p, self.size)
+
+    def __call__(self, image: Image.Image, boxes: List[List[float]]):
+        return self.apply(image, boxes, self.sample(*image.size))
 
 
 class VOCDetectionYOLO(Dataset):
@@ -171,8 +207,13 @@ class VOCDetectionYOLO(Dataset):
                           "(VOCdevkit/VOC<year>/...) and pass download=False")
 
     def __init__(self, root: str | Path = None, year: str = "2007", image_set: str = "train", download: bool = False, S: int = 7, B: int = 2,
-                 transform=None, target_size: Tuple[int, int] = (448, 448), augment: bool = True):
+                 transform=None, target_size: Tuple[int, int] = (448, 448), augment: bool = True, device_transform: bool = False):
         self.S, self.B = S, B
+        # device_transform: __getitem__ returns (decoded uint8 HWC tensor, AugParams, target) for yolo.augment.collate_u8 -- the crop,
+        # resize, colour jitter and normalisation then run on the device (yolo_augment_u8) with the very parameters drawn here
+        if device_transform and transform is not None:
+            raise ValueError("device_transform=True cannot run a custom `transform` on the device")
+        self.device_transform = device_transform
         self.C = len(self.VOC_CLASSES)
         self.target_size = target_size
         self.augment = augment and image_set == "train"            # only the training split is augmented (dataset.py:190)
@@ -214,19 +255,30 @@ class VOCDetectionYOLO(Dataset):
         annotation = parse_voc_xml(ET.parse(self.voc_dir / "Annotations" / f"{name}.xml").getroot())
         return image, annotation
 
+    def _augmented_target(self, annotation: dict, w: int, h: int, p: AugParams) -> torch.Tensor:
+        """target of a training sample whose image is cropped by ``p`` (the host and the device path alike)"""
+        bboxes, class_ids = self._extract_bboxes_from_annotation(annotation)
+        pix = [[(x - bw / 2) * w, (y - bh / 2) * h, (x + bw / 2) * w, (y + bh / 2) * h] for x, y, bw, bh in bboxes]
+        pix = crop_boxes(pix, p, self.target_size)
+        H, W = self.target_size
+        norm = []
+        for x0, y0, x1, y1 in pix:
+            clamp = lambda v: max(0, min(1, v))   # noqa: E731
+            norm.append([clamp(((x0 + x1) / 2) / W), clamp(((y0 + y1) / 2) / H), clamp((x1 - x0) / W), clamp((y1 - y0) / H)])
+        return self._encode_target(norm, class_ids)
+
     def __getitem__(self, idx: int):
         image, annotation = self._load(idx)
-        if self.augment and isinstance(self.transform, _Augment):
-            bboxes, class_ids = self._extract_bboxes_from_annotation(annotation)
-            w, h = image.size
-            pix = [[(x - bw / 2) * w, (y - bh / 2) * h, (x + bw / 2) * w, (y + bh / 2) * h] for x, y, bw, bh in bboxes]
-            image, pix = self.transform(image, pix)
-            H, W = self.target_size
-            norm = []
-            for x0, y0, x1, y1 in pix:
-                clamp = lambda v: max(0, min(1, v))   # noqa: E731
-                norm.append([clamp(((x0 + x1) / 2) / W), clamp(((y0 + y1) / 2) / H), clamp((x1 - x0) / W), clamp((y1 - y0) / H)])
-            return self._finish(image), self._encode_target(norm, class_ids)
+        w, h = image.size
+        augmented = self.augment and isinstance(self.transform, _Augment)
+        if self.device_transform:
+            p = self.transform.sample(w, h) if augmented else AugParams(0, 0, h, w)
+            target = self._augmented_target(annotation, w, h, p) if augmented else self._parse_voc_annotation(annotation)
+            return torch.from_numpy(np.asarray(image, dtype=np.uint8).copy()), p, target
+        if augmented:
+            p = self.transform.sample(w, h)
+            image, _ = self.transform.apply(image, [], p)
+            return self._finish(image), self._augmented_target(annotation, w, h, p)
         return self.transform(image), self._parse_voc_annotation(annotation)
 
     # ---- annotation handling: same names / arguments / results as the reference (dataset.py:411-532)
@@ -287,11 +339,12 @@ class CombinedVOCDataset(Dataset):
 
 
 def create_voc_datasets(years_and_splits: list, download: bool = True, S: int = 7, B: int = 2, target_size: Tuple[int, int] = (448, 448),
-                        augment: bool = True, root: str | Path = None) -> Dataset:
+                        augment: bool = True, root: str | Path = None, device_transform: bool = False) -> Dataset:
     """One VOCDetectionYOLO, or their concatenation, for [(year, image_set), ...] (dataset.py:662-730).  Offline, ``download``
     is honoured only as "the data must already lie under root" (default root: $VOC_ROOT or ./data)."""
     if root is None:
         root = os.environ.get("VOC_ROOT", "data")
-    datasets = [VOCDetectionYOLO(root=root, year=y, image_set=s, download=False, S=S, B=B, target_size=target_size, augment=augment)
+    datasets = [VOCDetectionYOLO(root=root, year=y, image_set=s, download=False, S=S, B=B, target_size=target_size, augment=augment,
+                                 device_transform=device_transform)
                 for y, s in years_and_splits]
     return datasets[0] if len(datasets) == 1 else CombinedVOCDataset(datasets)

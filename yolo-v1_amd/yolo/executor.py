@@ -420,14 +420,24 @@ class Plan:
     def forward(self, x: torch.Tensor, train: bool, drop_training: bool, u8_size=None):
         """x: NCHW fp32 device tensor -- or, with ``u8_size = (H, W)``, decoded uint8 images [N][h][w][3] that
         yolo_preprocess_u8 resizes + normalises straight into the stem's NHWC4 input buffer (no fp32 NCHW round trip).
+        ``x`` may also be a ``yolo.augment.U8Batch`` (decoded images of different sizes + their crop / colour parameters, in training too: the
+        stem's weight gradient reads the same NHWC4 buffer): yolo_augment_u8 fills the stem's input buffer.
         Returns (out, saved) -- out is (N, O) fp32 if the plan ends with an fc layer, else NCHW fp32 features."""
+        from .augment import U8Batch
         L_ = RT.lib()
         st = RT.stream()
         N = x.shape[0]
         dev = x.device
-        x = x.detach()
         stem_f32 = False
-        if u8_size is not None:
+        if isinstance(x, U8Batch):
+            key, ws = self._workspace(N, x.shape, dev, train)
+            self._pack_all(train)
+            a = ws["in"]
+            if not (a.C == 4 and a.halo == 3):
+                raise ValueError("uint8 input needs a plan that starts with the 7x7/s2 stem")
+            x.into_act(a)
+        elif u8_size is not None:
+            x = x.detach()
             from . import preprocess as _pp
             key, ws = self._workspace(N, (N, 3, u8_size[0], u8_size[1]), dev, train)
             self._pack_all(train)
@@ -436,6 +446,7 @@ class Plan:
                 raise ValueError("uint8 input needs a plan that starts with the 7x7/s2 stem")
             _pp.preprocess_u8_into(x, u8_size, a)
         else:
+            x = x.detach()
             if x.dim() != 4 or x.shape[1] != self.in_channels:
                 raise RuntimeError(f"expected input of shape (N, {self.in_channels}, H, W), got {tuple(x.shape)}")
             if x.dtype != torch.float32 or not x.is_contiguous():

@@ -217,9 +217,13 @@ class YOLOv1(_PlanOwner, nn.Module):
         return y.view(-1, self.S, self.S, self.B * 5 + self.num_classes)
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x: (N, 3, H, W) fp32 images, or a ``yolo.augment.U8Batch`` (decoded uint8 images + crop / colour parameters): the default
+        YOLOv1 augments it straight into the stem's input buffer, every other model takes its fp32 tensor (``U8Batch.to_tensor``)."""
         if x.is_cuda and self._fusable():
             y = engine.run_plan(self.hip_plan(), x, self.training)
         else:
+            if not isinstance(x, torch.Tensor):
+                x = x.to_tensor()
             y = self.head(self.backbone(x))
         if y.dim() == 2:
             y = y.view(-1, self.S, self.S, self.B * 5 + self.num_classes)
