@@ -421,7 +421,8 @@ int yolo_sumsq_f32(const float *g, long n, double *acc, yolo_stream_t stream);
 /* One tensor of torch.optim.Adam (amsgrad=False, L2 weight decay) in a single pass; `step` is the
  * 1-based step count.  If norm_sq != NULL the gradient is first scaled by
  * min(1, max_norm / (sqrt(*norm_sq) + 1e-6)) exactly as clip_grad_norm_ would have.  If p_bf16 != NULL
- * the updated parameter is also written as bf16 (same layout). */
+ * the updated parameter is also written as bf16 (same layout; 8-B aligned, p / g / exp_avg / exp_avg_sq 16-B aligned -- the same holds
+ * for every tensor of the multi-tensor forms -- else YOLO_E_UNSUPPORTED). */
 int yolo_adam_step(float *p, const float *g, float *exp_avg, float *exp_avg_sq, long n, float lr, float beta1,
                    float beta2, float eps, float weight_decay, long step, const double *norm_sq,
                    float max_norm, void *p_bf16, yolo_stream_t stream);

@@ -313,8 +313,11 @@ def test_hip_adam_matches_torch_adam():
         torch.nn.utils.clip_grad_norm_(pb, max_norm=10.0)
         ob.step()
         oa.step()
+        torch.cuda.synchronize()
         for p, q in zip(pa, pb):
             torch.testing.assert_close(p, q, rtol=2e-5, atol=2e-6)
+            for key in ("exp_avg", "exp_avg_sq"):       # both moments, not only the parameter they move
+                torch.testing.assert_close(oa.state[p][key], ob.state[q][key], rtol=2e-5, atol=2e-6)
     # stand-alone clip
     for p, q in zip(pa, pb):
         g = torch.randn_like(p) * 2

@@ -303,6 +303,7 @@ YOLO_API int yolo_adam_step(float *p, const float *g, float *m, float *v, long n
     if (!p || !g || !m || !v || n < 0 || step < 1) return fail(YOLO_E_ARG, "yolo_adam_step: bad argument");
     if (n == 0) return 0;
     if (((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) & 15) return fail(YOLO_E_UNSUPPORTED, "yolo_adam_step: pointers must be 16-B aligned");
+    if ((uintptr_t)p_bf16 & 7) return fail(YOLO_E_UNSUPPORTED, "yolo_adam_step: bf16 shadow is not 8-B aligned");   // 8-B stores, as the multi-tensor entries
     const double bc1 = 1.0 - pow((double)beta1, (double)step), bc2 = 1.0 - pow((double)beta2, (double)step);
     const float step_size = (float)((double)lr / bc1);
     const float inv_bc2_sqrt = (float)(1.0 / sqrt(bc2));
