@@ -453,6 +453,42 @@ int yolo_adam_step_multi(const yolo_adam_tensor *t, int count, float lr, float b
 int yolo_adam_step_multi_bg(const yolo_adam_tensor *t, int count, float lr, float beta1, float beta2, float eps,
                             float weight_decay, long step, const double *norm_sq, float max_norm, const float *skip_flag,
                             int workgroups, yolo_stream_t stream);
+
+/* torch.optim.SGD (maximize=False) with the same folded clip_grad_norm_, skip flag and bf16 shadow as the Adam entries -- the YOLOv1
+ * paper's recipe (momentum 0.9, weight decay 5e-4) in the optimizer slot of the reference's train step
+ * (src/yolo/training/trainer.py:79-95).  Per element, in fp32, every a * b + c one fused multiply-add (all three forms: the same bits):
+ *     g = grad * clip                   clip = min(1, max_norm / (sqrt(*norm_sq) + 1e-6)), 1 when norm_sq == NULL
+ *     g = g + weight_decay * p          (weight_decay != 0)
+ *     buf = first_step ? g : momentum * buf + (1 - dampening) * g ;  g = nesterov ? g + momentum * buf : buf      (momentum != 0)
+ *     p = p - lr * g ;  p_bf16 = bf16(p)
+ * first_step != 0: the momentum buffers are only written (torch creates them as a copy of the gradient).  momentum == 0: buf is not
+ * touched and may be NULL.  *skip_flag != 0 updates nothing: not p, not buf, not the shadow.
+ * YOLO_E_ARG: a null pointer, a negative size / lr / momentum / weight_decay, nesterov with momentum <= 0 or dampening != 0 (the
+ * ValueErrors of torch.optim.SGD), workgroups outside 1 .. 256, more than YOLO_MT_MAX tensors in the background form.
+ * YOLO_E_UNSUPPORTED: p / g / buf not 16-B aligned, p_bf16 not 8-B aligned.  Either way nothing is launched. */
+typedef struct yolo_sgd_tensor {
+    float *p;            /* parameter, updated in place */
+    const float *g;      /* gradient */
+    float *buf;          /* momentum_buffer */
+    void *p_bf16;        /* optional bf16 shadow of p in the same layout (NULL: none) */
+    long n;              /* elements */
+} yolo_sgd_tensor;
+/* One tensor (trainer.py:79-95, the optimizer.step() of one parameter). */
+int yolo_sgd_step(float *p, const float *g, float *buf, long n, float lr, float momentum, float dampening, float weight_decay,
+                  int nesterov, int first_step, const double *norm_sq, float max_norm, void *p_bf16, const float *skip_flag,
+                  yolo_stream_t stream);
+/* A whole parameter list (trainer.py:79-95, optimizer.step() as torch's multi-tensor `_foreach` SGD does it): one launch per
+ * YOLO_MT_MAX tensors, the host table copied into the kernel arguments; empty tensors are legal.  All tensors share first_step and
+ * the hyper-parameters. */
+int yolo_sgd_step_multi(const yolo_sgd_tensor *t, int count, float lr, float momentum, float dampening, float weight_decay,
+                        int nesterov, int first_step, const double *norm_sq, float max_norm, const float *skip_flag,
+                        yolo_stream_t stream);
+/* The same update (trainer.py:79-95) as a BACKGROUND pass for a second stream, like yolo_adam_step_multi_bg: `workgroups` (1 .. 256)
+ * persistent workgroups of 1024 threads, each holding one CU to itself.  At most YOLO_MT_MAX tensors. */
+int yolo_sgd_step_multi_bg(const yolo_sgd_tensor *t, int count, float lr, float momentum, float dampening, float weight_decay,
+                           int nesterov, int first_step, const double *norm_sq, float max_norm, const float *skip_flag,
+                           int workgroups, yolo_stream_t stream);
+
 /* g *= min(1, max_norm / (sqrt(*norm_sq) + 1e-6))  (stand-alone clip_grad_norm_ for other optimizers). */
 int yolo_clip_scale_f32(float *g, long n, const double *norm_sq, float max_norm, yolo_stream_t stream);
 

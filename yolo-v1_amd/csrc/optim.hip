@@ -13,7 +13,7 @@
 // 48 of them small; one launch per tensor leaves most of the chip idle for most of the step.  The
 // per-tensor table travels in the kernel arguments (<= YOLO_MT_MAX entries per launch), a workgroup
 // owns one MT_CHUNK-element slice of one tensor and finds it by scanning the table's chunk prefix.
-#include "common.h"
+#include "optim_common.h"
 
 namespace yolo {
 
@@ -86,7 +86,6 @@ __global__ void __launch_bounds__(256) adam_kernel(float *__restrict__ p, const 
     }
 }
 
-constexpr int MT_CHUNK = 8192;  // elements per workgroup: 256 lanes x float4 x 8
 constexpr int SQ_CHUNK = 65536; // the norm kernel ends in ONE fp64 atomic per workgroup on one address: keep them few
 
 struct SumsqTable {
@@ -100,13 +99,6 @@ struct AdamTable {
     int first[YOLO_MT_MAX + 1];
     int count;
 };
-
-__device__ __forceinline__ int find_tensor(const int *first, int count, int b)
-{
-    int i = 0;
-    while (i + 1 < count && first[i + 1] <= b) ++i;  // wave-uniform scalar scan of <= 48 entries
-    return i;
-}
 
 __global__ void __launch_bounds__(256) sumsq_multi_kernel(const SumsqTable tab, double *__restrict__ acc)
 {

@@ -38,6 +38,9 @@ def main():
     ap.add_argument("--epochs", type=int, default=135)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--weight-decay", type=float, default=5e-4)
+    ap.add_argument("--optimizer", choices=["adam", "sgd"], default="adam", help="sgd: the YOLOv1 paper's recipe (SGD with momentum)")
+    ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd only")
+    ap.add_argument("--nesterov", action="store_true", help="--optimizer sgd only")
     ap.add_argument("--lr-decay-epochs", default="75,105")
     ap.add_argument("--lambda-coord", type=float, default=5.0)
     ap.add_argument("--lambda-noobj", type=float, default=0.5)
@@ -86,14 +89,19 @@ def main():
     criterion = YOLOLoss(S=7, B=2, C=20, lambda_coord=a.lambda_coord, lambda_noobj=a.lambda_noobj)
     params = [p for p in model.parameters() if p.requires_grad]
     if device == "cuda":
-        from yolo.optim import Adam          # fused clip(10) + Adam on the HIP kernels
-        optimizer = Adam(params, lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=10.0)
+        from yolo.optim import SGD, Adam     # fused clip(10) + Adam / SGD with momentum on the HIP kernels
+        if a.optimizer == "sgd":
+            optimizer = SGD(params, lr=a.lr, momentum=a.momentum, weight_decay=a.weight_decay, nesterov=a.nesterov, max_grad_norm=10.0)
+        else:
+            optimizer = Adam(params, lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=10.0)
         if model._fusable():
             # the Linear layers' update runs as a background pass beside the next forward's conv stack (11.40 vs 11.58 ms per step
             # at batch 64: the persistent conv kernels draw their tiles from a queue, so the held CUs cost only their share)
             optimizer.attach_plan(model.hip_plan(), overlap=True)
         elif hasattr(model.head, "hip_plan"):          # DetectionHead on a ResNet trunk: its Linear layers' bf16 operands
             optimizer.attach_plan(model.head.hip_plan())
+    elif a.optimizer == "sgd":
+        optimizer = torch.optim.SGD(params, lr=a.lr, momentum=a.momentum, weight_decay=a.weight_decay, nesterov=a.nesterov)
     else:
         optimizer = torch.optim.Adam(params, lr=a.lr, weight_decay=a.weight_decay)
     scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=[int(e) for e in a.lr_decay_epochs.split(",")], gamma=0.1)

@@ -77,6 +77,12 @@ class AdamTensor(ctypes.Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("p_bf16", c_void_p), ("n", ctypes.c_long)]
 
 
+class SgdTensor(ctypes.Structure):
+    """struct yolo_sgd_tensor (include/yolo_hip.h)."""
+
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("buf", c_void_p), ("p_bf16", c_void_p), ("n", ctypes.c_long)]
+
+
 class ConvPackItem(ctypes.Structure):
     """struct yolo_conv_pack_item (include/yolo_hip.h)."""
 
@@ -168,6 +174,9 @@ _SIGS = {
     "yolo_sumsq_f32_multi": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
     "yolo_adam_step_multi": [ctypes.POINTER(AdamTensor), c_int, c_float, c_float, c_float, c_float, c_float, c_long, c_void_p, c_float, c_void_p, c_void_p],
     "yolo_adam_step_multi_bg": [ctypes.POINTER(AdamTensor), c_int, c_float, c_float, c_float, c_float, c_float, c_long, c_void_p, c_float, c_void_p, c_int, c_void_p],
+    "yolo_sgd_step": [c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
+    "yolo_sgd_step_multi": [ctypes.POINTER(SgdTensor), c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p],
+    "yolo_sgd_step_multi_bg": [ctypes.POINTER(SgdTensor), c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p],
     "yolo_bias_lrelu_rows": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "yolo_bias_lrelu_rows_slabs": [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
 }

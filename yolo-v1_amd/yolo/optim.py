@@ -1,4 +1,4 @@
-"""Optimizer step on the HIP kernels (optim.hip): Adam + global-norm gradient clipping in one HBM pass.
+"""Optimizer step on the HIP kernels (optim.hip, sgd.hip): Adam or SGD with momentum + global-norm gradient clipping in one HBM pass.
 
 ``Adam`` takes the constructor arguments of ``torch.optim.Adam`` (the reference builds
 ``optim.Adam(model.parameters(), lr=1e-4, weight_decay=5e-4)``, src/train.py:177-179) and keeps the
@@ -6,6 +6,9 @@ same per-parameter state (``step``, ``exp_avg``, ``exp_avg_sq``), so optimizer `
 interchangeable with the reference's checkpoints.  ``max_grad_norm`` folds
 ``clip_grad_norm_(params, max_norm)`` (trainer.py:79,93) into the same pass: the global norm is
 reduced on the device and read by the update kernel, no host sync.
+
+``SGD`` is ``torch.optim.SGD`` (the YOLOv1 paper's recipe: momentum 0.9, weight decay 5e-4) in the same slot, with the same
+``max_grad_norm``, ``skip_if``, ``attach_plan`` and second-stream pass; what the two share lives in ``_Fused``.
 """
 
 from __future__ import annotations
@@ -16,7 +19,7 @@ import ctypes
 import os
 
 from . import _hip
-from ._hip import AdamTensor, check, lib, ptr, stream
+from ._hip import AdamTensor, SgdTensor, check, lib, ptr, stream
 
 
 BG_CUS = 128       # CUs the background update of the Linear layers holds (yolo_adam_step_multi_bg): a CU streams ~42 GB/s whatever it keeps in flight,
@@ -89,19 +92,20 @@ def clip_grad_norm_(parameters, max_norm: float) -> torch.Tensor:
     return acc.sqrt().float()
 
 
-class Adam(torch.optim.Optimizer):
-    """torch.optim.Adam semantics (amsgrad=False, L2 weight decay) on yolo_adam_step."""
+class _Fused(torch.optim.Optimizer):
+    """What the fused optimizers share: the folded clip_grad_norm_ (``max_grad_norm``, with the attached plans' squared-norm hints), the
+    device-side skip flag (``skip_if``), the bf16 shadows of the Linear layers and their background pass on a second stream
+    (``attach_plan``, ``synchronize``), one multi-tensor launch per group of parameters.  A subclass supplies its state and table entry
+    (``_entry``), its two launches (``_launch``) and the same step in stock torch ops for CPU parameters (``_step_on_cpu``)."""
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm: float | None = None):
-        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
-            raise ValueError("invalid Adam hyper-parameter")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
+    def __init__(self, params, defaults, max_grad_norm: float | None = None):
+        super().__init__(params, defaults)
         self.max_grad_norm = max_grad_norm
         self.bf16_shadow: dict[int, tuple] = {}   # id(param) -> (bf16 tensor refreshed in the same pass, callback(param) | None)
         self.plans: list = []                     # attached engine plans: their backward passes leave squared gradient norms (grad_norm_sq)
         # attach_plan(plan, overlap=True): id(param) -> plan.  The update of these parameters (the Linear layers: 76 % of the model's
         # optimizer bytes, first used at the END of the next forward) runs as a background pass on BG_CUS CUs of a second stream
-        # (yolo_adam_step_multi_bg) beside the next forward's conv stack; the plan's forward waits for it in front of its first
+        # (yolo_adam_step_multi_bg / yolo_sgd_step_multi_bg) beside the next forward's conv stack; the plan's forward waits for it in front of its first
         # Linear layer.
         self.deferred: dict[int, object] = {}
         self._side = None
@@ -128,81 +132,43 @@ class Adam(torch.optim.Optimizer):
         with torch.cuda.device(all_params[0].device):
             return self._step_on_device(all_params, loss)
 
-    def _step_on_cpu(self, all_params):
-        """CPU parameters (the reference's ``--device cpu`` runs, the gloo tests of the data-parallel path): the same step in stock
-        torch ops -- clip coefficient min(1, max_norm / (|g| + 1e-6)) from the squared norms (incl. the plans' hints), then the
-        arithmetic of adam1 in optim.hip, which is torch.optim.Adam's."""
+    def _known_norms(self) -> dict:
+        """squared gradient norms the attached plans' backward passes left (grad_norm_sq): one backward pass, one use"""
         known = {}
         for plan in self.plans:
             known.update(plan.grad_norm_sq)
             plan.grad_norm_sq.clear()
-        clip = 1.0
-        if self.max_grad_norm is not None:
-            total = float(grad_norm_sq(all_params, known).sqrt())
-            clip = min(1.0, self.max_grad_norm / (total + 1e-6))
-        skip, self.skip_if = self.skip_if, None
-        if skip is not None and float(skip) != 0.0:
-            return
-        for group in self.param_groups:
-            b1, b2 = group["betas"]
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                state = self.state[p]
-                if len(state) == 0:
-                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                state["step"] += 1
-                t = int(state["step"].item())
-                g = p.grad.float() * clip + group["weight_decay"] * p
-                state["exp_avg"].lerp_(g, 1.0 - b1)
-                state["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1.0 - b2)
-                denom = state["exp_avg_sq"].sqrt() / ((1.0 - b2 ** t) ** 0.5) + group["eps"]
-                p.addcdiv_(state["exp_avg"], denom, value=-group["lr"] / (1.0 - b1 ** t))
+        return known
 
     def _step_on_device(self, all_params, loss):
-        known = {}
-        for plan in self.plans:
-            known.update(plan.grad_norm_sq)
-            plan.grad_norm_sq.clear()          # one backward pass, one use
-        norm = grad_norm_sq(all_params, known) if self.max_grad_norm is not None else None
+        norm = grad_norm_sq(all_params, self._known_norms()) if self.max_grad_norm is not None else None
         skip, self.skip_if = self.skip_if, None
         if skip is not None:
             if not (skip.is_cuda and skip.dtype == torch.float32 and skip.numel() == 1):
                 raise ValueError("skip_if must be one float32 on the device")
             _hip.require_cuda(all_params[0], skip)
-        st = stream()
         main_t = torch.cuda.current_stream()
         side_used = False
         for group in self.param_groups:
-            b1, b2 = group["betas"]
-            # one launch per (group, step count, foreground / background): normally one for the conv stack and one for the Linear layers
-            by_step: dict[tuple, list] = {}
+            # one launch per (group, key of the subclass, foreground / background): normally one for the conv stack and one for the Linear layers
+            by_key: dict[tuple, list] = {}
             keep = []                      # temporaries the launch reads must outlive the enqueue
             for p in group["params"]:
                 if p.grad is None:
                     continue
                 if p.dtype != torch.float32 or not p.is_contiguous():
-                    raise RuntimeError("yolo.optim.Adam needs contiguous fp32 parameters")
+                    raise RuntimeError(f"yolo.optim.{type(self).__name__} needs contiguous fp32 parameters")
                 g = _f32c(p.grad)
                 keep.append(g)
-                state = self.state[p]
-                if len(state) == 0:
-                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                state["step"] += 1
                 hook = self.bf16_shadow.get(id(p))
-                shadow = hook[0] if hook is not None else None
                 late = OVERLAP and id(p) in self.deferred
                 if late:
                     g.record_stream(self._side_stream())     # read on the second stream after the caller may have dropped it
-                by_step.setdefault((int(state["step"].item()), late), []).append(
-                    (p, AdamTensor(p.data_ptr(), g.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(),
-                                   shadow.data_ptr() if shadow is not None else None, p.numel()), hook))
-            for (step, late), items in sorted(by_step.items(), key=lambda kv: kv[0][1]):      # the foreground launch first
-                tab = (AdamTensor * len(items))(*[it[1] for it in items])
+                key, entry = self._entry(group, p, g, hook[0] if hook is not None else None)
+                by_key.setdefault((key, late), []).append((p, entry, hook))
+            for (key, late), items in sorted(by_key.items(), key=lambda kv: kv[0][1]):      # the foreground launch first
+                tab = (type(items[0][1]) * len(items))(*[it[1] for it in items])
+                side = None
                 if late and len(items) <= 48:
                     side = self._side_stream()
                     if not side_used:
@@ -212,12 +178,7 @@ class Adam(torch.optim.Optimizer):
                         if skip is not None:
                             skip.record_stream(side)
                         side_used = True
-                    check(lib().yolo_adam_step_multi_bg(tab, len(items), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                                        float(group["weight_decay"]), step, ptr(norm), float(self.max_grad_norm or 0.0), ptr(skip), BG_CUS,
-                                                        ctypes.c_void_p(side.cuda_stream)), "yolo_adam_step_multi_bg")
-                else:
-                    check(lib().yolo_adam_step_multi(tab, len(items), float(group["lr"]), float(b1), float(b2), float(group["eps"]),
-                                                     float(group["weight_decay"]), step, ptr(norm), float(self.max_grad_norm or 0.0), ptr(skip), st), "yolo_adam_step_multi")
+                self._launch(group, key, tab, len(items), norm, skip, side)
                 for p, _, hook in items:
                     # the kernel updated p through a raw pointer: bump the autograd version so that the
                     # engine's packed bf16 copies notice (no memory traffic) ...
@@ -295,3 +256,136 @@ class Adam(torch.optim.Optimizer):
             self._hook_owner(plan)
         if all(pl is not plan for pl in self.plans):
             self.plans.append(plan)
+
+
+class Adam(_Fused):
+    """torch.optim.Adam semantics (amsgrad=False, L2 weight decay) on yolo_adam_step."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm: float | None = None):
+        if lr < 0 or eps < 0 or not (0 <= betas[0] < 1) or not (0 <= betas[1] < 1) or weight_decay < 0:
+            raise ValueError("invalid Adam hyper-parameter")
+        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay), max_grad_norm)
+
+    def _step_on_cpu(self, all_params):
+        """CPU parameters (the reference's ``--device cpu`` runs, the gloo tests of the data-parallel path): the same step in stock
+        torch ops -- clip coefficient min(1, max_norm / (|g| + 1e-6)) from the squared norms (incl. the plans' hints), then the
+        arithmetic of adam1 in optim.hip, which is torch.optim.Adam's."""
+        known = self._known_norms()
+        clip = 1.0
+        if self.max_grad_norm is not None:
+            total = float(grad_norm_sq(all_params, known).sqrt())
+            clip = min(1.0, self.max_grad_norm / (total + 1e-6))
+        skip, self.skip_if = self.skip_if, None
+        if skip is not None and float(skip) != 0.0:
+            return
+        for group in self.param_groups:
+            b1, b2 = group["betas"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                state = self.state[p]
+                if len(state) == 0:
+                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
+                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+                state["step"] += 1
+                t = int(state["step"].item())
+                g = p.grad.float() * clip + group["weight_decay"] * p
+                state["exp_avg"].lerp_(g, 1.0 - b1)
+                state["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1.0 - b2)
+                denom = state["exp_avg_sq"].sqrt() / ((1.0 - b2 ** t) ** 0.5) + group["eps"]
+                p.addcdiv_(state["exp_avg"], denom, value=-group["lr"] / (1.0 - b1 ** t))
+
+    def _entry(self, group, p, g, shadow):
+        state = self.state[p]
+        if len(state) == 0:
+            state["step"] = torch.tensor(0.0, dtype=torch.float32)
+            state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+        state["step"] += 1
+        return int(state["step"].item()), AdamTensor(p.data_ptr(), g.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(),
+                                                     shadow.data_ptr() if shadow is not None else None, p.numel())
+
+    def _launch(self, group, step, tab, count, norm, skip, side):
+        b1, b2 = group["betas"]
+        h = (float(group["lr"]), float(b1), float(b2), float(group["eps"]), float(group["weight_decay"]), step, ptr(norm),
+             float(self.max_grad_norm or 0.0), ptr(skip))
+        if side is not None:
+            check(lib().yolo_adam_step_multi_bg(tab, count, *h, BG_CUS, ctypes.c_void_p(side.cuda_stream)), "yolo_adam_step_multi_bg")
+        else:
+            check(lib().yolo_adam_step_multi(tab, count, *h, stream()), "yolo_adam_step_multi")
+
+
+class SGD(_Fused):
+    """torch.optim.SGD semantics (momentum, dampening, L2 weight decay, Nesterov; maximize=False) on yolo_sgd_step_multi: the state is
+    ``momentum_buffer`` per parameter, created on the first step, and the param groups carry torch's keys, so ``state_dict()`` loads into
+    ``torch.optim.SGD`` and the other way round.
+
+    One edge: a step that ``skip_if`` cancels on the device while it is a parameter's very first one leaves the new momentum buffer at
+    zero, and the host has already counted it as created -- the next step then takes ``momentum * 0 + (1 - dampening) * g`` where torch
+    would copy ``g`` (the same unless dampening != 0).  The reference raises inside the loss forward in that situation and training ends;
+    so it does here, when the training loop reads the loss ``parts`` of the flagged step."""
+
+    def __init__(self, params, lr=1e-3, momentum=0, dampening=0, weight_decay=0, nesterov=False, max_grad_norm: float | None = None):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(params, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay, nesterov=nesterov,
+                                      maximize=False, foreach=None, differentiable=False, fused=None), max_grad_norm)
+
+    def _step_on_cpu(self, all_params):
+        """CPU parameters: the same step in stock torch ops -- the clip coefficient formed in fp32 as the kernels form it
+        (sgd_begin in sgd.hip, which is clip_grad_norm_'s), then torch.optim.SGD's own sequence of operations."""
+        known = self._known_norms()
+        clip = None
+        if self.max_grad_norm is not None:
+            total = grad_norm_sq(all_params, known).sqrt().float()
+            clip = (torch.tensor(self.max_grad_norm, dtype=torch.float32) / (total + torch.tensor(1e-6, dtype=torch.float32))).clamp(max=1.0)
+        skip, self.skip_if = self.skip_if, None
+        if skip is not None and float(skip) != 0.0:
+            return
+        for group in self.param_groups:
+            momentum, wd = group["momentum"], group["weight_decay"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                g = p.grad.float()
+                if clip is not None:
+                    g = g * clip
+                if wd != 0:
+                    g = g.add(p, alpha=wd)
+                if momentum != 0:
+                    state = self.state[p]
+                    buf = state.get("momentum_buffer")
+                    if buf is None:
+                        buf = state["momentum_buffer"] = g.clone()
+                    else:
+                        buf.mul_(momentum).add_(g, alpha=1 - group["dampening"])
+                    g = g.add(buf, alpha=momentum) if group["nesterov"] else buf
+                p.add_(g, alpha=-group["lr"])
+
+    def _entry(self, group, p, g, shadow):
+        buf, first = None, False
+        if group["momentum"] != 0:
+            state = self.state[p]
+            buf = state.get("momentum_buffer")
+            first = buf is None
+            if first:
+                buf = state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            elif not (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()):
+                raise RuntimeError("yolo.optim.SGD needs contiguous fp32 momentum buffers on the device")
+        return first, SgdTensor(p.data_ptr(), g.data_ptr(), buf.data_ptr() if buf is not None else None,
+                                shadow.data_ptr() if shadow is not None else None, p.numel())
+
+    def _launch(self, group, first, tab, count, norm, skip, side):
+        h = (float(group["lr"]), float(group["momentum"]), float(group["dampening"]), float(group["weight_decay"]), int(bool(group["nesterov"])),
+             int(first), ptr(norm), float(self.max_grad_norm or 0.0), ptr(skip))
+        if side is not None:
+            check(lib().yolo_sgd_step_multi_bg(tab, count, *h, BG_CUS, ctypes.c_void_p(side.cuda_stream)), "yolo_sgd_step_multi_bg")
+        else:
+            check(lib().yolo_sgd_step_multi(tab, count, *h, stream()), "yolo_sgd_step_multi")
