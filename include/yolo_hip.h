@@ -254,11 +254,21 @@ typedef struct yolo_wgrad_desc {
     float *slabs;                    /* optional (variant 5 / 6, accumulate = 0, Cin % 4 == 0): scratch of slab_floats floats.  Every workgroup then
                                         STORES its 256 x 256 partial tile there and a second kernel adds the partials of a tile in pixel-range
                                         order into dw -- no fp32 atomics on dw (1.5 TB/s chip-wide, 60-90 k cycles per workgroup), dw need not
-                                        be zero-filled, and dw is bit-reproducible.  yolo_wgrad_slab_floats gives the size a launch needs */
+                                        be zero-filled, and dw is bit-reproducible.  yolo_wgrad_slab_floats gives the size a launch needs.
+                                        Variants 0 / 1 / 4 (the 128 x 128 kernels; uniform split and split = 0, pair_taps, pixel geometry): only
+                                        the workgroups of a tile that IS split over pixel ranges store a dense 128 x 128 partial; a tile owned by
+                                        one workgroup keeps its direct store.  This replaces the atomicAdd epilogue of wgrad_kernel /
+                                        wgrad8_kernel.  With slabs in use, db is order-fixed too: the bias sums of the pixel ranges are stored
+                                        ([co][range]: behind the tile partials for variants 0 / 1 / 4; in row co of dw, which is free until the
+                                        slab sum runs, for 5 / 6 -- KH * KW * Cin must hold the ranges) and added in range order into db by a
+                                        plain store, so db need not be zero-filled.  A launch of variant 0 / 1 / 4 without a split tile needs
+                                        no slabs (yolo_wgrad_slab_floats gives 0) and runs as without them: db += one sum per channel.
+                                        Variants 2 / 3 and accumulate != 0 are refused (YOLO_E_UNSUPPORTED) */
     int64_t slab_floats;
 } yolo_wgrad_desc;
 
-/* floats of yolo_wgrad_desc.slabs the launch described by d would use (0: the variant has no slab mode); launches nothing */
+/* floats of yolo_wgrad_desc.slabs the launch described by d would use (0: variants 2 / 3; variants 0 / 1 / 4 when no tile is split);
+ * host arithmetic only, launches nothing */
 int yolo_wgrad_slab_floats(const yolo_wgrad_desc *d, long *floats);
 int yolo_wgrad(const yolo_wgrad_desc *d, const void *x_bf16, const void *dy_bf16,
                float *dw_packed, float *db, yolo_stream_t stream);
@@ -443,6 +453,16 @@ typedef struct yolo_adam_tensor {
     long n;              /* elements */
 } yolo_adam_tensor;
 int yolo_sumsq_f32_multi(const float *const *g, const long *n, int count, double *acc, yolo_stream_t stream);
+/* Order-fixed forms of yolo_sumsq_f32 / yolo_sumsq_f32_multi (norm_fixed.hip; EngineConfig.DETERMINISTIC).  They replace the one fp64
+ * atomicAdd per workgroup in which sumsq_kernel / sumsq_multi_kernel end: a workgroup owns one 65536-element slice of one tensor (the
+ * table layout of yolo_sumsq_f32_multi) and STORES its fp64 partial in scratch slot = its index; a last one-workgroup stage adds the slots
+ * in a fixed order onto *acc (caller zero-fills, as before).  The double is then a function of the gradients and the tensor list alone,
+ * and with it the clip coefficient of every parameter.  scratch: scratch_slots >= yolo_sumsq_fixed_slots doubles, 8-B aligned, not shared
+ * with a launch in flight on another stream.  Everything is checked before the first launch. */
+int yolo_sumsq_fixed_slots(const long *n, int count, long *slots);
+int yolo_sumsq_f32_fixed(const float *g, long n, double *scratch, long scratch_slots, double *acc, yolo_stream_t stream);
+int yolo_sumsq_f32_multi_fixed(const float *const *g, const long *n, int count, double *scratch, long scratch_slots, double *acc,
+                               yolo_stream_t stream);
 int yolo_adam_step_multi(const yolo_adam_tensor *t, int count, float lr, float beta1, float beta2, float eps,
                          float weight_decay, long step, const double *norm_sq, float max_norm, const float *skip_flag,
                          yolo_stream_t stream);

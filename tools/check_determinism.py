@@ -31,3 +31,43 @@ for (co, ci, k, hw) in ((1024, 512, 3, 28), (512, 256, 3, 56), (1024, 1024, 3, 1
         if ref is None: ref = outs[0].float()
         rel = ((outs[0].float() - ref).norm() / ref.norm()).item()
         print(f"co {co} ci {ci} k {k} hw {hw} hint {hint:2d}: deterministic={same} max differing elems={nd} rel vs hint1={rel:.2e}")
+
+# ---- training-step leg: N steps twice from one seed under EngineConfig.DETERMINISTIC, a hash of every parameter and optimizer-state tensor after each
+# (usage: check_determinism.py [steps [batch [adam|sgd]]]; with the switch left off -- YOLO_AMD_DETERMINISTIC=0 -- the hashes normally differ)
+import hashlib
+import synth
+from yolo import YOLOLoss, YOLOv1
+from yolo.config import CONFIG
+from yolo.optim import SGD, Adam
+if "YOLO_AMD_DETERMINISTIC" not in os.environ:
+    CONFIG.DETERMINISTIC = True
+steps = int(sys.argv[1]) if len(sys.argv) > 1 else 3
+batch = int(sys.argv[2]) if len(sys.argv) > 2 else 8
+kind = sys.argv[3] if len(sys.argv) > 3 else "adam"
+xb = torch.from_numpy(synth.synth_images(batch, 0)).to(dev)
+tb = torch.from_numpy(synth.synth_targets(batch, 1)).to(dev)
+runs = []
+for rep in range(2):
+    torch.manual_seed(0)
+    model = YOLOv1().to(dev).train()
+    ps = list(model.parameters())
+    opt = SGD(ps, lr=1e-3, momentum=0.9, weight_decay=5e-4, max_grad_norm=10.0) if kind == "sgd" else Adam(ps, lr=1e-4, weight_decay=5e-4, max_grad_norm=10.0)
+    opt.attach_plan(model.hip_plan(), overlap=True)
+    crit, hs = YOLOLoss(), []
+    for s in range(steps):
+        torch.manual_seed(1 + s)
+        loss, _ = crit(model(xb), tb)
+        opt.zero_grad(set_to_none=True)
+        loss.backward()
+        opt.step()
+        opt.synchronize()
+        torch.cuda.synchronize()
+        h = hashlib.sha256()
+        for n, p in model.named_parameters():
+            for t in [p] + [v for _, v in sorted(opt.state[p].items()) if torch.is_tensor(v)]:
+                h.update(t.detach().cpu().contiguous().reshape(-1).view(torch.uint8).numpy().tobytes())
+        hs.append(h.hexdigest())
+    runs.append(hs)
+    del model, opt
+for s, (a, b) in enumerate(zip(*runs)):
+    print(f"training step {s + 1} ({kind}, batch {batch}, DETERMINISTIC={CONFIG.DETERMINISTIC}): {'same' if a == b else 'DIFFERENT'}  {a[:16]} {b[:16]}")

@@ -99,8 +99,8 @@ __global__ void __launch_bounds__(256, 2) wgrad_kernel(const WgradParams p)
     int bid;
     long pbeg, pend;
     bool atomic;
-    int part_unused;
-    wgrad_map(p, nwg, bid, pbeg, pend, atomic, part_unused);
+    int part;
+    wgrad_map(p, nwg, bid, pbeg, pend, atomic, part);
     if (pbeg >= pend) return;   // empty range of a rounded-up split (the whole workgroup leaves)
     // co-tile fastest, then ci-tile, then tap: neighbours share the x tile of one tap
     const int co_tile = bid % p.n_co_tiles;
@@ -234,7 +234,10 @@ __global__ void __launch_bounds__(256, 2) wgrad_kernel(const WgradParams p)
         for (int t = 0; t < 2; ++t) {
             const float tot = bsum[t] + __shfl_xor(bsum[t], 32, 64);  // the two k-halves of each co row
             const int co = co0 + wco * 64 + t * 32 + (lane & 31);
-            if (lane < 32 && co < p.Cout) atomicAdd(p.db + co, tot);
+            if (lane < 32 && co < p.Cout) {
+                if (p.bias_part) p.bias_part[(long)co * p.bias_ld + wgrad_range(p, bid, part)] = tot;   // slab mode: summed in range order afterwards
+                else atomicAdd(p.db + co, tot);
+            }
         }
     }
 
@@ -244,6 +247,7 @@ __global__ void __launch_bounds__(256, 2) wgrad_kernel(const WgradParams p)
     const long ldw = (long)p.ntaps * p.Cin;
     float *ot = reinterpret_cast<float *>(bufA);
     const bool vec_ok = !atomic && (p.Cin & 3) == 0 && ((uintptr_t)p.dw & 15) == 0;
+    float *slab = (atomic && p.slabs) ? p.slabs + wgrad_slab_index(p, part) * (WG_T * WG_T) : nullptr;
     float ssq = 0.0f;      // p.sumsq: squares of the values this thread stores (the host requires the vector store path for it)
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
@@ -258,7 +262,14 @@ __global__ void __launch_bounds__(256, 2) wgrad_kernel(const WgradParams p)
                         ot[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * WG_T + wci * 64 + j * 32 + (lane & 31)] = acc[i][j][r];
         }
         __syncthreads();
-        if (vec_ok) {
+        if (slab) {
+            // slab mode, split tile: the whole 128 x 128 partial, dense, as 16-B stores (wgrad_slab_sum128_kernel adds them in range order)
+#pragma unroll
+            for (int it = 0; it < 8; ++it) {
+                const int idx = it * 256 + tid, row = idx >> 5, c4 = (idx & 31) * 4;
+                *reinterpret_cast<float4 *>(slab + (h * 64 + row) * WG_T + c4) = *reinterpret_cast<const float4 *>(ot + row * WG_T + c4);
+            }
+        } else if (vec_ok) {
 #pragma unroll
             for (int it = 0; it < 8; ++it) {
                 const int idx = it * 256 + tid, row = idx >> 5, c4 = (idx & 31) * 4;
@@ -343,8 +354,8 @@ __global__ void __launch_bounds__(512, 2) wgrad8_kernel(const WgradParams p)
     int bid;
     long pbeg, pend;
     bool atomic;
-    int part_unused;
-    wgrad_map(p, nwg, bid, pbeg, pend, atomic, part_unused);
+    int part;
+    wgrad_map(p, nwg, bid, pbeg, pend, atomic, part);
     if (pbeg >= pend) return;   // empty range of a rounded-up split (the whole workgroup leaves)
     // co-tile fastest, then ci-tile, then tap: neighbours share the x tile of one tap
     const int co_tile = bid % p.n_co_tiles;
@@ -476,7 +487,10 @@ __global__ void __launch_bounds__(512, 2) wgrad8_kernel(const WgradParams p)
         for (int t = 0; t < 1; ++t) {
             const float tot = bsum[t] + __shfl_xor(bsum[t], 32, 64);  // the two k-halves of each co row
             const int co = co0 + wco * 32 + (lane & 31);
-            if (lane < 32 && co < p.Cout) atomicAdd(p.db + co, tot);
+            if (lane < 32 && co < p.Cout) {
+                if (p.bias_part) p.bias_part[(long)co * p.bias_ld + wgrad_range(p, bid, part)] = tot;   // slab mode: summed in range order afterwards
+                else atomicAdd(p.db + co, tot);
+            }
         }
     }
 
@@ -486,6 +500,7 @@ __global__ void __launch_bounds__(512, 2) wgrad8_kernel(const WgradParams p)
     const long ldw = (long)p.ntaps * p.Cin;
     float *ot = reinterpret_cast<float *>(bufA);
     const bool vec_ok = !atomic && (p.Cin & 3) == 0 && ((uintptr_t)p.dw & 15) == 0;
+    float *slab = (atomic && p.slabs) ? p.slabs + wgrad_slab_index(p, part) * (WG_T * WG_T) : nullptr;
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         __syncthreads();   // (first pass: every wave is done reading the stage buffers)
@@ -497,7 +512,14 @@ __global__ void __launch_bounds__(512, 2) wgrad8_kernel(const WgradParams p)
                     ot[((wco & 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5)) * WG_T + wci * 64 + j * 32 + (lane & 31)] = acc[0][j][r];
         }
         __syncthreads();
-        if (vec_ok) {
+        if (slab) {
+            // slab mode, split tile: the whole 128 x 128 partial, dense, as 16-B stores (wgrad_slab_sum128_kernel adds them in range order)
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int idx = it * 512 + tid, row = idx >> 5, c4 = (idx & 31) * 4;
+                *reinterpret_cast<float4 *>(slab + (h * 64 + row) * WG_T + c4) = *reinterpret_cast<const float4 *>(ot + row * WG_T + c4);
+            }
+        } else if (vec_ok) {
 #pragma unroll
             for (int it = 0; it < 4; ++it) {
                 const int idx = it * 512 + tid, row = idx >> 5, c4 = (idx & 31) * 4;
@@ -994,6 +1016,51 @@ __global__ void __launch_bounds__(256) stem_wgrad_reduce_kernel(const float *__r
     }
 }
 
+// Slab mode of the 128 x 128 kernels: sum of a split tile's dense partials into the packed gradient dw[co][tap][ci], in pixel-range order
+// (fixed: the result does not depend on the order in which the workgroups ran).  One thread = 4 consecutive columns of one tile row;
+// grid = (16, tiles).  A tile of an unsplit segment was stored by its one workgroup and is left alone.  `atomic` = WgradParams.atomic
+// (bit 0 / 1: main / tail segment is split); uniform split: main_tiles = every tile, main_split = the ranges.
+__global__ void __launch_bounds__(256) wgrad_slab_sum128_kernel(const float *__restrict__ slabs, float *__restrict__ dw, int Cout, int Cin, int ntaps, int n_co_tiles,
+                                                                int n_ci_tiles, int pair_taps, int atomic, int main_tiles, int main_split, int tail_split,
+                                                                int main_ranges, int tail_ranges)
+{
+    const int bid = blockIdx.y;
+    const bool tail = bid >= main_tiles;
+    if (!((atomic >> (tail ? 1 : 0)) & 1)) return;
+    const int idx = blockIdx.x * 256 + threadIdx.x;               // float4 inside the tile: row = idx / 32
+    const int row = idx >> 5, c4 = (idx & 31) * 4;
+    const int co_tile = bid % n_co_tiles, rest = bid / n_co_tiles;
+    const int ci_tile = rest % n_ci_tiles, tap_tile = rest / n_ci_tiles;
+    const int tap = pair_taps ? 2 * tap_tile : tap_tile;
+    const int ci0 = ci_tile * WG_T;
+    const int col_lim = pair_taps ? (tap + 1 < ntaps ? 2 * Cin : Cin) : Cin - ci0;
+    const int co = co_tile * WG_T + row;
+    if (co >= Cout || c4 >= col_lim) return;
+    const long first = tail ? ((atomic & 1) ? (long)main_tiles * main_split : 0L) + (long)(bid - main_tiles) * tail_split : (long)bid * main_split;
+    const int n = tail ? tail_ranges : main_ranges;
+    const float *src = slabs + first * (WG_T * WG_T) + row * WG_T + c4;
+    float4 a = *reinterpret_cast<const float4 *>(src);
+    for (int r = 1; r < n; ++r) {
+        const float4 b = *reinterpret_cast<const float4 *>(src + (long)r * (WG_T * WG_T));
+        a.x += b.x; a.y += b.y; a.z += b.z; a.w += b.w;
+    }
+    *reinterpret_cast<float4 *>(dw + (long)co * ntaps * Cin + (long)tap * Cin + ci0 + c4) = a;
+}
+
+// Slab mode, bias gradient: db[co] = sum over the pixel ranges r of part[co * ld + r], in range order (plain store: db need not be zero).
+// The partials come from the (tap 0, ci-tile 0) workgroups, whose tile number is their co tile.
+__global__ void __launch_bounds__(256) wgrad_bias_sum_kernel(const float *__restrict__ part, long ld, int Cout, int tile_co, int main_tiles, int main_ranges,
+                                                             int tail_ranges, float *__restrict__ db)
+{
+    const int co = blockIdx.x * 256 + threadIdx.x;
+    if (co >= Cout) return;
+    const int n = co / tile_co >= main_tiles ? tail_ranges : main_ranges;
+    const float *src = part + (long)co * ld;
+    float s = src[0];
+    for (int r = 1; r < n; ++r) s += src[r];
+    db[co] = s;
+}
+
 // db[c] += sum_p dy[p][c]  (bias gradient).  HBM-bound column sum: a workgroup covers w <= 256
 // 8-channel chunks (one 16-B load per thread) x R = 256/w pixel rows per pass, so every wave reads
 // whole contiguous pixel rows whatever the channel count; LDS reduction over R, one fp32 atomic per
@@ -1106,6 +1173,15 @@ static int wgrad_stem7_impl(const void *x_nhwc4, const void *dy, int N, int Ho, 
 
 static int wgrad_run(const yolo_wgrad_desc *d, const void *x, const void *dy, float *dw, float *db, yolo_stream_t stream, long *query);
 
+namespace yolo {
+int wgrad_bias_sum_launch(const WgradParams &p, int tile_co, int tiles, int main_ranges, int tail_ranges, float *db, hipStream_t s)
+{
+    hipLaunchKernelGGL(wgrad_bias_sum_kernel, dim3((unsigned)((p.Cout + 255) / 256)), dim3(256), 0, s, (const float *)p.bias_part, p.bias_ld, p.Cout, tile_co,
+                       p.seg ? p.main_tiles : tiles, main_ranges, tail_ranges, db);
+    return check_launch("yolo_wgrad (bias sum)");
+}
+}  // namespace yolo
+
 YOLO_API int yolo_wgrad(const yolo_wgrad_desc *d, const void *x, const void *dy, float *dw, float *db, yolo_stream_t stream)
 {
     return wgrad_run(d, x, dy, dw, db, stream, nullptr);
@@ -1216,7 +1292,7 @@ static int wgrad_run(const yolo_wgrad_desc *d, const void *x, const void *dy, fl
         // slab mode (variant 5): partial tiles as plain stores + a fixed-order sum instead of fp32 atomics
         int main_ranges = 1, tail_ranges = 1;
         if (d->slabs || query) {
-            long need = 0;
+            long need = 0, bias_at = 0, bias_ld = 0;
             if (pipe) {
                 long nparts;
                 if (d->split > 0) {
@@ -1228,21 +1304,57 @@ static int wgrad_run(const yolo_wgrad_desc *d, const void *x, const void *dy, fl
                     tail_ranges = (int)std::min<long>(p.tail_split, (d->P + p.per_tail - 1) / p.per_tail);
                 }
                 need = nparts * 256 * 256;
+            } else if (!big) {
+                // 128 x 128 kernels: only the tiles of a SPLIT segment go through slabs (a tile owned by one workgroup keeps its direct store);
+                // behind the tile partials, [co][range] bias partials of the widest segment
+                long nparts;
+                int max_ranges;
+                if (d->split > 0) {
+                    main_ranges = (int)grid.y;
+                    nparts = grid.y > 1 ? (long)tiles * grid.y : 0;
+                    max_ranges = (int)grid.y;
+                } else {
+                    nparts = (p.main_split > 1 ? (long)p.main_tiles * p.main_split : 0) + (p.tail_split > 1 ? (long)p.tail_tiles * p.tail_split : 0);
+                    main_ranges = (int)std::min<long>(p.main_split, (d->P + p.per_main - 1) / p.per_main);
+                    tail_ranges = (int)std::min<long>(p.tail_split, (d->P + p.per_tail - 1) / p.per_tail);
+                    max_ranges = std::max(p.main_tiles > 0 ? p.main_split : 1, p.tail_tiles > 0 ? p.tail_split : 1);
+                }
+                bias_at = nparts * WG_T * WG_T;
+                bias_ld = max_ranges;
+                need = nparts > 0 ? bias_at + (long)p.n_co_tiles * WG_T * max_ranges : 0;
             }
             if (query) {
                 *query = need;
                 return 0;
             }
-            if (!pipe || d->accumulate || (d->Cin & 3) || (((uintptr_t)dw | (uintptr_t)d->slabs) & 15))
-                return fail(YOLO_E_UNSUPPORTED, "yolo_wgrad: slabs need variant 5, accumulate = 0, Cin %% 4 == 0 and 16-B aligned dw / slabs");
+            if (big || d->accumulate || (d->Cin & 3) || (((uintptr_t)dw | (uintptr_t)d->slabs) & 15))
+                return fail(YOLO_E_UNSUPPORTED, "yolo_wgrad: slabs need variant 0 / 1 / 4 / 5 / 6, accumulate = 0, Cin %% 4 == 0 and 16-B aligned dw / slabs");
             if (d->slab_floats < need) return fail(YOLO_E_ARG, "yolo_wgrad: slabs hold %ld floats, this launch needs %ld (yolo_wgrad_slab_floats)", (long)d->slab_floats, need);
-            p.slabs = d->slabs;
-            p.atomic = 0;
+            if (pipe) {
+                p.slabs = d->slabs;
+                p.atomic = 0;
+                if (db) {
+                    // every tile goes through the slabs, so dw is free until the slab sum runs: row co holds the bias partials of its ranges
+                    if (std::max(main_ranges, tail_ranges) > (long)p.ntaps * p.Cin)
+                        return fail(YOLO_E_UNSUPPORTED, "yolo_wgrad: slabs with db need KH * KW * Cin >= the pixel ranges of a tile");
+                    p.bias_part = dw;
+                    p.bias_ld = (long)p.ntaps * p.Cin;
+                }
+            } else if (need > 0) {
+                p.slabs = d->slabs;          // p.atomic keeps saying which segment is split
+                if (db) {
+                    p.bias_part = d->slabs + bias_at;
+                    p.bias_ld = bias_ld;
+                }
+            }
         }
         if (d->dw_sumsq && (pipe || big || d->variant == 4 || p.atomic || (d->Cin & 3) || ((uintptr_t)dw & 15)))
             return fail(YOLO_E_UNSUPPORTED, "yolo_wgrad: dw_sumsq needs the 128 x 128 kernel storing every tile from one workgroup (split 1, no accumulate, Cin %% 4 == 0)");
         if (pipe) {
             if (int rc = d->variant == 6 ? wgrad_wide_launch(p, grid, s) : wgrad_pipe_launch(p, grid, s)) return rc;
+            if (p.bias_part) {            // (reads its partials out of dw: in front of the slab sum, which overwrites them)
+                if (int rc = wgrad_bias_sum_launch(p, 256, tiles, main_ranges, tail_ranges, db, s)) return rc;
+            }
             if (p.slabs) {
                 if (int rc = wgrad_slab_sum_launch(p, tiles, main_ranges, tail_ranges, s)) return rc;
             }
@@ -1263,6 +1375,15 @@ static int wgrad_run(const yolo_wgrad_desc *d, const void *x, const void *dy, fl
             hipLaunchKernelGGL(wgrad_kernel, grid, dim3(256), 0, s, p);
         }
         if (int rc = check_launch("yolo_wgrad")) return rc;
+        if (p.slabs && !pipe) {
+            hipLaunchKernelGGL(wgrad_slab_sum128_kernel, dim3(WG_T * WG_T / 4 / 256, (unsigned)tiles), dim3(256), 0, s, (const float *)p.slabs, p.dw, p.Cout, p.Cin,
+                               p.ntaps, p.n_co_tiles, p.n_ci_tiles, p.pair_taps, p.atomic, p.seg ? p.main_tiles : tiles, p.seg ? p.main_split : main_ranges,
+                               p.seg ? p.tail_split : 1, main_ranges, tail_ranges);
+            if (int rc = check_launch("yolo_wgrad (slab sum)")) return rc;
+            if (p.bias_part) {
+                if (int rc = wgrad_bias_sum_launch(p, WG_T, tiles, main_ranges, tail_ranges, db, s)) return rc;
+            }
+        }
     }
     if (db && !dw) {
         const int nchunks = (d->Cout + 7) / 8;

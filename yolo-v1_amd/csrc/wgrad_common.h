@@ -20,7 +20,11 @@ struct WgradParams {
     float *db;              // optional: bias gradient, accumulated by the (tap 0, ci-tile 0) workgroups
     double *sumsq;          // optional (128 x 128 kernel, tiles stored by ONE workgroup): += sum of squares of the dw this launch writes
     float *slabs;           // optional (wgrad_pipe.hip): every workgroup STORES its 256 x 256 partial tile at slabs + part * 65536 (part = its
-                            // (tile, pixel range) number, see wgrad_map) instead of adding it to dw; wgrad_slab_sum_kernel adds them up in range order
+                            // (tile, pixel range) number, see wgrad_map) instead of adding it to dw; wgrad_slab_sum_kernel adds them up in range order.
+                            // wgrad.hip (128 x 128 tiles): only the workgroups of a SPLIT tile do (dense 128 x 128 partials, numbered over the split
+                            // segments alone, wgrad_slab_index); a tile owned by one workgroup keeps its direct store
+    float *bias_part;       // optional (slab mode with db): the (tap 0, ci-tile 0) workgroups STORE their bias sums at bias_part[co * bias_ld + range]
+    long bias_ld;           // instead of adding them to db; wgrad_bias_sum_kernel adds them up in range order
     long P;                 // pixels to reduce over
     // pixel p -> slot in the dy / x buffers.  gW == 0: p is the slot ("flat" indexing).  Else p = (n*gH + oy)*gW + ox and
     // slot = n*g_img + oy*g_row + ox*g_px + g_off (interior pixels of a zero-haloed buffer, optionally every 2nd one);
@@ -90,6 +94,19 @@ __device__ __forceinline__ void wgrad_map(const WgradParams &p, int nwg, int &bi
     }
 }
 
+// pixel range of a workgroup inside its tile (wgrad_map's `part` minus the tile's first part)
+__device__ __forceinline__ int wgrad_range(const WgradParams &p, int bid, int part)
+{
+    if (!p.seg) return (int)blockIdx.y;
+    return bid < p.main_tiles ? part - bid * p.main_split : part - p.main_tiles * p.main_split - (bid - p.main_tiles) * p.tail_split;
+}
+
+// 128 x 128 kernels, slab mode: slab of partial `part`.  Only split segments own slabs: with an unsplit main segment the tail's come first.
+__device__ __forceinline__ long wgrad_slab_index(const WgradParams &p, int part)
+{
+    return (p.seg && !(p.atomic & 1)) ? (long)part - (long)p.main_tiles * p.main_split : (long)part;
+}
+
 #define GLDS16(gptr, lptr) \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr), (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
 
@@ -99,6 +116,8 @@ int wgrad_pipe_launch(const WgradParams &p, dim3 grid, hipStream_t s);
 int wgrad_wide_launch(const WgradParams &p, dim3 grid, hipStream_t s);
 // ... slab mode: sum of the partial tiles into the packed gradient (main_ranges / tail_ranges = pixel ranges that hold pixels)
 int wgrad_slab_sum_launch(const WgradParams &p, int tiles, int main_ranges, int tail_ranges, hipStream_t s);
+// ... and of the bias partials (WgradParams.bias_part) into db, in range order; tile_co = rows of a co tile (128 / 256)
+int wgrad_bias_sum_launch(const WgradParams &p, int tile_co, int tiles, int main_ranges, int tail_ranges, float *db, hipStream_t s);
 // igemm.hip: the debug buffer of yolo_debug_stamps (diagnostic builds)
 void debug_stamp_target(long **buf, int *it);
 

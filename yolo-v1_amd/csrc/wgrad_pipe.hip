@@ -359,7 +359,10 @@ __global__ void __launch_bounds__(wp::NTHR, 2) wgrad_pipe_kernel(const WgradPara
         for (int t = 0; t < 4; ++t) {
             const float tot = bsum[t] + __shfl_xor(bsum[t], 32, 64);  // the two k-halves of each co row
             const int co = co0 + wco * 128 + t * 32 + (lane & 31);
-            if (lane < 32 && co < p.Cout) atomicAdd(p.db + co, tot);
+            if (lane < 32 && co < p.Cout) {
+                if (p.bias_part) p.bias_part[(long)co * p.bias_ld + wgrad_range(p, bid, part)] = tot;   // slab mode: summed in range order afterwards
+                else atomicAdd(p.db + co, tot);
+            }
         }
     }
 

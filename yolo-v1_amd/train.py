@@ -29,6 +29,16 @@ from yolo.dataset import SyntheticYOLODataset, create_voc_datasets  # noqa: E402
 from yolo.parallel import broadcast_parameters  # noqa: E402
 
 
+def _seed_worker(worker_id: int) -> None:
+    """DataLoader worker: numpy and ``random`` from the seed torch derived for this worker from the loader's generator"""
+    import random
+
+    import numpy as np
+    s = torch.initial_seed() % (1 << 31)
+    np.random.seed(s)
+    random.seed(s)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
@@ -54,7 +64,26 @@ def main():
     ap.add_argument("--device-augment", action="store_true",
                     help="VOC only: loaders ship decoded uint8 images + sampled parameters, crop / resize / colour jitter / normalise run on the device")
     ap.add_argument("--voc-root", default=None, help="dataset root (default: $VOC_ROOT or ./data)")
+    ap.add_argument("--deterministic", action="store_true",
+                    help="EngineConfig.DETERMINISTIC: every order-dependent sum of the training step runs order-fixed (bit-reproducible steps and --resume)")
+    ap.add_argument("--seed", type=int, default=None, help="seed of torch, numpy, random and the loaders (every epoch starts from (seed, epoch))")
     a = ap.parse_args()
+    if a.deterministic:
+        if a.backbone == "resnet50":
+            # (the training loop puts the whole model in train(): there is no eval-mode trunk to ask for here)
+            from yolo.models import BN_STATS_NOT_DETERMINISTIC
+            ap.error(BN_STATS_NOT_DETERMINISTIC)
+        from yolo.config import CONFIG
+        CONFIG.DETERMINISTIC = True
+        if a.seed is None:
+            a.seed = 0
+    gen, worker_init = None, None
+    if a.seed is not None:
+        from yolo.training.trainer import seed_epoch
+        seed_epoch(a.seed, 0)                 # parameter initialisation
+        gen = torch.Generator()
+        gen.manual_seed(a.seed)
+        worker_init = _seed_worker
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -79,8 +108,9 @@ def main():
         collate = collate_u8
     sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank) if world > 1 else None
     train_loader = DataLoader(train_ds, batch_size=a.batch_size, shuffle=sampler is None, sampler=sampler, num_workers=a.num_workers,
-                              pin_memory=device == "cuda", drop_last=True, collate_fn=collate)
-    val_loader = DataLoader(val_ds, batch_size=a.batch_size, shuffle=False, num_workers=a.num_workers, pin_memory=device == "cuda", collate_fn=collate)
+                              pin_memory=device == "cuda", drop_last=True, collate_fn=collate, generator=gen, worker_init_fn=worker_init)
+    val_loader = DataLoader(val_ds, batch_size=a.batch_size, shuffle=False, num_workers=a.num_workers, pin_memory=device == "cuda", collate_fn=collate,
+                            worker_init_fn=worker_init)
 
     backbone = YOLOv1Backbone() if a.backbone == "yolov1" else ResNetBackbone(pretrained=not a.no_pretrained, freeze=a.freeze_backbone)
     model = YOLOv1(backbone=backbone, num_classes=20, S=7, B=2).to(device)
@@ -121,7 +151,8 @@ def main():
         ckdir.mkdir(parents=True, exist_ok=True)
     res = training.train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, a.epochs, ckdir,
                          save_frequency=a.save_frequency, compute_map=a.compute_map, start_epoch=start_epoch,
-                         best_val_loss_init=best_val, best_map_init=best_map)
+                         best_val_loss_init=best_val, best_map_init=best_map, seed=a.seed,
+                         record={"seed": a.seed, "deterministic": bool(a.deterministic)} if a.seed is not None else None)
     if rank == 0:
         print("done:", res)
     if world > 1:

@@ -172,6 +172,9 @@ _SIGS = {
     "yolo_pack_conv_weights_multi": [ctypes.POINTER(ConvPackItem), c_int, c_void_p],
     "yolo_unpack_conv_wgrads_multi": [ctypes.POINTER(ConvUnpackItem), c_int, c_void_p],
     "yolo_sumsq_f32_multi": [c_void_p, c_void_p, c_int, c_void_p, c_void_p],
+    "yolo_sumsq_fixed_slots": [ctypes.POINTER(c_long), c_int, ctypes.POINTER(c_long)],
+    "yolo_sumsq_f32_fixed": [c_void_p, c_long, c_void_p, c_long, c_void_p, c_void_p],
+    "yolo_sumsq_f32_multi_fixed": [c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p, c_void_p],
     "yolo_adam_step_multi": [ctypes.POINTER(AdamTensor), c_int, c_float, c_float, c_float, c_float, c_float, c_long, c_void_p, c_float, c_void_p, c_void_p],
     "yolo_adam_step_multi_bg": [ctypes.POINTER(AdamTensor), c_int, c_float, c_float, c_float, c_float, c_float, c_long, c_void_p, c_float, c_void_p, c_int, c_void_p],
     "yolo_sgd_step": [c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p],

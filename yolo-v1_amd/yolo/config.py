@@ -49,6 +49,10 @@ class EngineConfig:
     PLAN_TIMES: object = None        # dict: igemm_call records (start, end) events per problem key -- in-situ time of the plan in use (tools/merge_plans.py)
     TUNE_REPS: int = 1               # tuner: launches per timed sample (1: a single launch behind a cache flush; > 1: back-to-back launches, warm caches -- the regime inside a forward pass)
     FC_WGRAD_SIDE: bool = True       # the Linear layers' weight gradients on the second stream too: the 822 MB store of the big one runs beside the 411 MB read of its data gradient
+    DETERMINISTIC: bool = False      # training: every order-dependent sum of a YOLOv1 / DetectionHead step runs order-fixed -- slabs on every yolo_wgrad launch (128 x 128 kernels
+                                     # included), bias gradients summed in range order, the gradient norm through yolo_sumsq_f32_multi_fixed, no dw_sumsq, a ("splitk", ..) plan
+                                     # run as ("slabs", ..).  Same inputs, weights and plan table -> the same bits, run to run and process to process.
+                                     # Not covered: BatchNorm batch statistics of a trainable ResNet trunk (NotImplementedError), the order of a cross-rank all-reduce
     WGRAD_WIDE: bool = True          # ... variant 6 (wgrad_wide.hip: four waves of 128 x 128, accumulators in AGPRs) instead of 5, and on more layers
 
 

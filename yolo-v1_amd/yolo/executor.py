@@ -739,6 +739,7 @@ class Plan:
         # kernel leaves the matrix cores idle -- overlap with the data-gradient kernels of the layers below, workgroup by workgroup.
         main_t = RT.STREAMS.current(dev)
         side_t = self._side_stream(dev) if self.c.WGRAD_STREAM else None
+        det = bool(self.c.DETERMINISTIC)     # every yolo_wgrad launch with slabs (scratch per stream), no norm hint (EngineConfig.DETERMINISTIC)
 
         def _on_side():
             return _on_side_stream(main_t, side_t, self.on_stream_wait if self.arena is not None else None)
@@ -785,7 +786,9 @@ class Plan:
                 dw, db = grad_tensors(li)
                 wd = WgradDesc(N, ldg, L.Cin, L.Cout, L.Cin, 1, 1, 0, 0, 1, 0)
                 nsq = None
-                if L.Cout * L.Cin >= self.c.FC_NORM_IN_WGRAD and L.Cin % 4 == 0:
+                if det:
+                    pass      # the norm hint ends in one fp64 atomic per workgroup: the optimizer's order-fixed pass reads this gradient instead
+                elif L.Cout * L.Cin >= self.c.FC_NORM_IN_WGRAD and L.Cin % 4 == 0:
                     # the kernel that stores this gradient also sums its squares: the optimizer's global-norm pass (clip_grad_norm_) then
                     # need not read the 822 MB of the Linear behind nn.Flatten again (yolo.optim.grad_norm_sq, `known`)
                     nsq = torch.zeros((), dtype=torch.float64, device=dev)
@@ -795,10 +798,14 @@ class Plan:
                     # the 411 MB of weights (2.7 TB/s alone); side by side they share the memory system instead of taking turns
                     fc_keep.append(gb)          # (a temporary of the main stream's allocator that the second stream reads: alive until the streams join)
                     with _on_side() as wst:
+                        if det:
+                            _attach_wgrad_slabs(L_, wd, dev, wst)
                         with _timed(f"fc{li}.wgrad", "wgrad", 2.0 * N * L.Cout * L.Cin):
                             check(L_.yolo_wgrad(ctypes.byref(wd), ptr(xin), ptr(gb), ptr(dw), ptr(db), wst), f"wgrad fc{li}")
                         self._layer_done(li)
                 else:
+                    if det:
+                        _attach_wgrad_slabs(L_, wd, dev, st)
                     with _timed(f"fc{li}.wgrad", "wgrad", 2.0 * N * L.Cout * L.Cin):
                         check(L_.yolo_wgrad(ctypes.byref(wd), ptr(xin), ptr(gb), ptr(dw), ptr(db), st), f"wgrad fc{li}")
                     self._layer_done(li)
@@ -822,6 +829,9 @@ class Plan:
                     check(L_.yolo_transpose_bf16(ptr(gb), N, L.Cout, ldg, ptr(gT), ldn, st), "transpose g")
                     dxT = torch.zeros((L.Cin, N), dtype=torch.float32, device=dev)
                     wd = WgradDesc(L.Cout, L.Cin, ldn, L.Cin, N, 1, 1, 0, 0, 0, 1)   # split 0: library's schedule (0.095 vs 0.135 ms with 3 ranges)
+                    if det:
+                        wd.accumulate = 0       # (dxT is zero: the same value) the pixel ranges of a tile as slabs, on this stream's own scratch
+                        _attach_wgrad_slabs(L_, wd, dev, st)
                     with _timed(f"fc{li}.dgrad", "wgrad", 2.0 * N * L.Cout * L.Cin):
                         check(L_.yolo_wgrad(ctypes.byref(wd), ptr(gT), ptr(wf), ptr(dxT), None, st), f"dgrad fc{li}")
                     if Lc.kind == "conv":
@@ -919,6 +929,8 @@ class Plan:
                         dwp = scratch[o: o + L.Cout * 7 * 8 * 4]
                         split = max(1, min(1024, g.slots // 4096))
                         wd = WgradDesc(g.slots, g.px_stride, xcol.px_stride, L.Cout, 7 * 32, 1, 1, 0, xcol.row_stride, split, 0)
+                        if det:
+                            _attach_wgrad_slabs(L_, wd, dev, wst)
                         with _timed(f"conv{li}.wgrad", "wgrad", 2.0 * N * L.Hout * L.Wout * L.Cout * 147):
                             check(L_.yolo_wgrad(ctypes.byref(wd), xcol.p, g.p, ptr(dwp), ptr(db), wst), "wgrad conv0")
                     else:
@@ -928,8 +940,8 @@ class Plan:
                         # (measured: worth it from 28x28 down and for stride 2; at 56x56 and above the halo is < 8 % of the slots
                         # and the per-row coordinate arithmetic costs more than it saves)
                         wd = self._wgrad_desc(L, g, xin, N)
-                        if self.c.WGRAD_SLABS and wd.variant >= 5:
-                            _attach_wgrad_slabs(L_, wd, dev)
+                        if det or (self.c.WGRAD_SLABS and wd.variant >= 5):
+                            _attach_wgrad_slabs(L_, wd, dev, wst)
                         with _timed(f"conv{li}.wgrad", "wgrad", 2.0 * N * L.Hout * L.Wout * L.Cout * L.Cin * L.K * L.K):
                             check(L_.yolo_wgrad(ctypes.byref(wd), xin.p, g.p, ptr(dwp), ptr(db), wst), f"wgrad conv{li}")
                     if not stem_direct:

@@ -21,6 +21,12 @@ import torch
 import torch.nn as nn
 
 from . import engine
+from .config import CONFIG
+
+
+BN_STATS_NOT_DETERMINISTIC = ("EngineConfig.DETERMINISTIC does not cover the ResNet trunk in training mode: its BatchNorm batch statistics are summed with "
+                              "fp64 atomics (bn.hip, the bn_stats epilogues of the conv kernels).  Put the trunk in eval() mode (running statistics; the "
+                              "DetectionHead behind it is covered), or use --backbone yolov1")
 
 
 class _PlanOwner:
@@ -125,6 +131,8 @@ class ResNetBackbone(Backbone):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.is_cuda:
+            if self.training and CONFIG.DETERMINISTIC:
+                raise NotImplementedError(BN_STATS_NOT_DETERMINISTIC)
             if self._plan is None:
                 self._plan = engine.ResNetPlan(self.extractor)
             if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):

@@ -20,6 +20,7 @@ import os
 
 from . import _hip
 from ._hip import AdamTensor, SgdTensor, check, lib, ptr, stream
+from .config import CONFIG as CFG
 
 
 BG_CUS = 128       # CUs the background update of the Linear layers holds (yolo_adam_step_multi_bg): a CU streams ~42 GB/s whatever it keeps in flight,
@@ -58,10 +59,33 @@ def grad_norm_sq(params, known=None) -> torch.Tensor:
         if grads:
             gp = (ctypes.c_void_p * len(grads))(*[g.data_ptr() for g in grads])
             gn = (ctypes.c_long * len(grads))(*[g.numel() for g in grads])
-            check(lib().yolo_sumsq_f32_multi(gp, gn, len(grads), ptr(acc), stream()), "yolo_sumsq_f32_multi")
+            if CFG.DETERMINISTIC:
+                # workgroup partials into scratch slots + a fixed-order last stage: the double, and with it the clip coefficient of every
+                # parameter, no longer depends on the order in which fp64 atomics arrived
+                slots = ctypes.c_long(0)
+                check(lib().yolo_sumsq_fixed_slots(gn, len(grads), ctypes.byref(slots)), "yolo_sumsq_fixed_slots")
+                st = stream()
+                scratch = _norm_scratch(dev, st, slots.value)
+                check(lib().yolo_sumsq_f32_multi_fixed(gp, gn, len(grads), ptr(scratch), scratch.numel(), ptr(acc), st), "yolo_sumsq_f32_multi_fixed")
+            else:
+                check(lib().yolo_sumsq_f32_multi(gp, gn, len(grads), ptr(acc), stream()), "yolo_sumsq_f32_multi")
         for e in extra:
             acc += e
     return acc
+
+
+_NORM_SCRATCH: dict = {}
+
+
+def _norm_scratch(dev, st, slots: int) -> torch.Tensor:
+    """fp64 scratch of the order-fixed norm, one per device and stream (launches of one stream use it one after the other), grown on demand"""
+    key = (dev.index, st.value or 0)
+    buf = _NORM_SCRATCH.get(key)
+    if buf is None or buf.numel() < slots:
+        if buf is not None:
+            buf.record_stream(torch.cuda.current_stream(dev))
+        buf = _NORM_SCRATCH[key] = torch.empty(max(slots, 1), dtype=torch.float64, device=dev)
+    return buf
 
 
 def _split_known(params, known):

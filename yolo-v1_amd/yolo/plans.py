@@ -192,6 +192,8 @@ def _run_plan_igemm(L_, d: IgemmDesc, plan, inp, w, bias, aux, out, st, what):
         elif isinstance(plan[0], int) and plan[0] == 19 and d.epilogue != EPI_NONE:
             plan = (10, plan[1])           # the streaming 1x1 kernel accumulates statistics of raw conv outputs only
     d.tile_px, d.px_begin, d.px_end, d.skew_phases, d.skew_step = 0, 0, 0, 0, 0
+    if plan[0] == "splitk" and CFG.DETERMINISTIC:
+        plan = ("slabs", plan[1], plan[2], 0)       # the same hint and split count, partial tiles added in fixed order instead of fp32 atomics
     if plan[0] in ("splitk", "slabs"):
         # few-pixel deep-K layer: S workgroups per output tile into a dense fp32 scratch (atomics, or one slab per split),
         # then the epilogue as a separate pass (yolo_igemm_finish)

@@ -99,19 +99,29 @@ def _splitk_scratch(n: int, zero: bool) -> torch.Tensor:
 
 
 _WGRAD_SLAB_BUF: dict = {}
+_WGRAD_SLAB_OLD: list = []
 
 
-def _attach_wgrad_slabs(L_, wd: WgradDesc, dev) -> None:
-    """slab mode of the pipelined weight-gradient kernel (yolo_wgrad_desc.slabs): partial tiles as plain stores + a fixed-order sum
-    instead of fp32 atomics.  One scratch per device, grown on demand (the launches of one stream use it one after the other)."""
+def _attach_wgrad_slabs(L_, wd: WgradDesc, dev, st=None) -> None:
+    """slab mode of the weight-gradient kernels (yolo_wgrad_desc.slabs): partial tiles as plain stores + a fixed-order sum
+    instead of fp32 atomics.  One scratch per device AND per stream ``st`` (the hipStream_t the launch goes to; None: the current one), grown on
+    demand: the launches of one stream use it one after the other, launches of two streams (the data-gradient chain and the weight-gradient
+    stream of the backward pass) may be in flight together and never share it."""
     need = ctypes.c_long(0)
     check(L_.yolo_wgrad_slab_floats(ctypes.byref(wd), ctypes.byref(need)), "wgrad_slab_floats")
     if need.value <= 0:
         return
-    key = torch.device(dev).index
+    if st is None:
+        st = RT.stream()
+    key = (torch.device(dev).index, getattr(st, "value", st) or 0)
     buf = _WGRAD_SLAB_BUF.get(key)
     if buf is None or buf.numel() < need.value:
+        old = buf
         buf = _WGRAD_SLAB_BUF[key] = torch.empty(need.value, dtype=torch.float32, device=dev)
+        if old is not None:
+            # the smaller buffer may still be read by a launch in flight on ``st``, which is not necessarily torch's current stream:
+            # keep it alive instead of handing it back to the allocator of another stream
+            _WGRAD_SLAB_OLD.append(old)
     wd.slabs, wd.slab_floats = buf.data_ptr(), buf.numel()
 
 

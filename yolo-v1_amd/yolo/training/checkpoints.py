@@ -1,6 +1,6 @@
 """Checkpoint files with the reference's dictionary keys (src/yolo/training/checkpoints.py:32-113), so
 checkpoints are interchangeable in both directions: ``epoch, model_state_dict, optimizer_state_dict,
-[scheduler_state_dict], [train_loss], val_loss, [mAP50:95, mAP50, mAP75]``."""
+[scheduler_state_dict], [train_loss], val_loss, [mAP50:95, mAP50, mAP75]`` (+ ``seed``, ``deterministic`` from ``train.py --seed / --deterministic``)."""
 
 from __future__ import annotations
 
@@ -24,8 +24,9 @@ def _with_map(data: dict, val_losses: dict) -> dict:
     return data
 
 
-def save_checkpoint(checkpoint_path: Path, epoch: int, model, optimizer, scheduler, train_losses: dict, val_losses: dict) -> None:
-    data = {"epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
+def save_checkpoint(checkpoint_path: Path, epoch: int, model, optimizer, scheduler, train_losses: dict, val_losses: dict, record: dict | None = None) -> None:
+    """``record``: extra plain entries (train.py: ``seed``, ``deterministic``) -- keys the reference's loader never reads, so the file still loads there"""
+    data = {**(record or {}), "epoch": epoch, "model_state_dict": model.state_dict(), "optimizer_state_dict": optimizer.state_dict(),
             "scheduler_state_dict": scheduler.state_dict(), "train_loss": float(train_losses["total"]), "val_loss": float(val_losses["total"])}
     _atomic_save(_with_map(data, val_losses), checkpoint_path)
     print(f"  checkpoint saved: {checkpoint_path}")

@@ -93,16 +93,37 @@ def validate(model, dataloader, criterion, device, compute_map: bool = False, nu
     return results
 
 
+def seed_epoch(seed: int, epoch: int, train_loader=None) -> None:
+    """all generators of the process from (seed, epoch); the loader's own generator (shuffling, the base seed of its workers) too"""
+    import random
+
+    import numpy as np
+    s = (int(seed) * 1000003 + int(epoch)) % (1 << 31)
+    torch.manual_seed(s)                # host generator and every device's
+    np.random.seed(s)
+    random.seed(s)
+    gen = getattr(train_loader, "generator", None)
+    if gen is not None:
+        gen.manual_seed(s)
+
+
 def train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, num_epochs: int, checkpoint_dir,
           save_frequency: int = 5, writer=None, compute_map: bool = False, map_frequency: int = 5, num_classes: int = 20,
-          start_epoch: int = 1, best_val_loss_init: float = None, best_map_init: float = None, scaler=None) -> dict[str, float]:
+          start_epoch: int = 1, best_val_loss_init: float = None, best_map_init: float = None, scaler=None,
+          seed: int | None = None, record: dict | None = None) -> dict[str, float]:
     """Epoch loop with the reference's checkpoint policy: latest every epoch, every ``save_frequency``
-    epochs, best validation loss, best mAP50:95."""
+    epochs, best validation loss, best mAP50:95.
+
+    ``seed``: every epoch starts from generators seeded by (seed, epoch) -- torch (host and device: the dropout masks), numpy, ``random`` and
+    the train loader's shuffling generator -- so epoch e of a resumed run draws what epoch e of the uninterrupted run drew, and no generator
+    state has to travel in the checkpoint.  ``record``: extra plain entries for the epoch checkpoints (train.py: seed, deterministic)."""
     best_val = float("inf") if best_val_loss_init is None else best_val_loss_init
     best_map = 0.0 if best_map_init is None else best_map_init
     final_train = None
     for epoch in range(start_epoch, num_epochs + 1):
         print(f"\n===== Epoch {epoch}/{num_epochs} =====")
+        if seed is not None:
+            seed_epoch(seed, epoch, train_loader)
         tr = train_epoch(model, train_loader, criterion, optimizer, device, epoch, writer, scaler)
         print("  train:", {k: round(v, 4) for k, v in tr.items()})
         want_map = compute_map and (epoch % map_frequency == 0 or epoch == num_epochs)
@@ -121,9 +142,9 @@ def train(model, train_loader, val_loader, criterion, optimizer, scheduler, devi
         # ranks wait, so that nobody runs ahead of a file that a later --resume on all ranks would read
         writer_rank = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
         if writer_rank:
-            save_checkpoint(checkpoint_dir / "yolo_latest.pth", epoch, model, optimizer, scheduler, tr, va)
+            save_checkpoint(checkpoint_dir / "yolo_latest.pth", epoch, model, optimizer, scheduler, tr, va, record)
             if epoch % save_frequency == 0:
-                save_checkpoint(checkpoint_dir / f"yolo_epoch_{epoch}.pth", epoch, model, optimizer, scheduler, tr, va)
+                save_checkpoint(checkpoint_dir / f"yolo_epoch_{epoch}.pth", epoch, model, optimizer, scheduler, tr, va, record)
         if va["total"] < best_val:
             best_val = va["total"]
             if writer_rank:
