@@ -7,9 +7,11 @@ modules' ``forward`` is bypassed and the plan drives libyolo_hip.so:
   * activations: zero-haloed NHWC bf16 buffers with a guard band (``runtime.Act``), allocated once per (batch, mode) and reused; producers only ever
     write the interior, so halos stay zero;
   * weights: bf16 panels re-packed from the fp32 masters only when a parameter's version changes;
-  * forward = one yolo_igemm per conv / Linear (+ pool / flatten helpers), launched with the problem's plan (``plans.igemm_call``);
+  * forward = one yolo_igemm per conv / Linear (+ pool / flatten helpers), launched with the problem's plan (``plans.igemm_call``); ``Plan.forward`` is a
+    loop over the layers that hands each to the ``_fwd_*`` step of its kind;
   * backward = per conv one yolo_wgrad (on a second stream) + one yolo_igemm data-gradient whose epilogue applies the previous LeakyReLU's
-    derivative (or a pool backward).
+    derivative (or a pool backward): ``Plan.backward`` walks the layers the other way through the ``_bwd_*`` steps, which share a ``_Backward`` state;
+  * descriptors are filled by the builders of ``runtime`` (``igemm_desc``, ``desc_aux``, ``rows_desc``), nowhere else.
 
 Everything is enqueued on the current PyTorch stream (and the plan's side stream); there is no host synchronisation.  Switches: ``plan.cfg`` (an
 ``EngineConfig``) if set, else the process-wide ``config.CONFIG``."""
@@ -26,7 +28,9 @@ from . import _hip
 from ._hip import (EPI_BIAS, EPI_BIAS_LRELU, EPI_MUL_DLRELU, EPI_NONE, ConvPackItem, ConvUnpackItem, IgemmDesc, PoolDesc, WgradDesc, check, ptr)
 from .config import CONFIG as CFG
 from .plans import igemm_call
-from .runtime import RT, Act, _attach_wgrad_slabs, _EventSlot, _igemm, _on_side_stream, _round_up, _timed
+from .runtime import (RT, Act, _attach_wgrad_slabs, _EventSlot, _igemm, _on_side_stream, _round_up, _timed, desc_aux, igemm_desc, rows_desc,
+                      stem_tiles_ok)
+
 
 @dataclass
 class Layer:
@@ -43,7 +47,7 @@ class Layer:
     weight: nn.Parameter | None = None
     bias: nn.Parameter | None = None
     first: bool = False            # the 3-channel 7x7/s2 stem (NHWC4 input, row-segment taps)
-    # geometry, filled by Plan._shape
+    # geometry of the workspace in use: Plan._workspace computes it, Plan._apply_geom puts it back
     Hin: int = 0
     Win: int = 0
     Hout: int = 0
@@ -376,25 +380,28 @@ class Plan:
 
     # ------------------------------------------------------------------ descriptors
     def _conv_desc(self, L: Layer, a_in: Act, a_out: Act) -> IgemmDesc:
-        d = IgemmDesc()
-        d.N, d.Ho, d.Wo = a_in.N, L.Hout, L.Wout
-        d.in_img_stride, d.in_row_stride, d.in_px_stride = a_in.img_stride, a_in.row_stride, a_in.px_stride
-        d.stride = L.stride
-        if L.first:
-            d.in_off = 0
-            d.KH, d.KW, d.tap_len = 7, 1, 32
+        if L.first:          # row-segment taps: 7 rows of 8 pixels x 4 channels, read from the buffer's first slot (the halo of 3 is the padding)
+            d = igemm_desc(a_in.N, L.Hout, L.Wout, L.stride, 7, 1, 32, L.Cout, a_in, 0, a_out)
         else:
-            d.in_off = a_in.interior_off(L.pad)
-            d.KH, d.KW, d.tap_len = L.K, L.K, L.Cin
-        d.Cout = L.Cout
-        d.out_img_stride, d.out_row_stride, d.out_px_stride = a_out.img_stride, a_out.row_stride, a_out.px_stride
-        d.out_off = a_out.interior_off()
-        d.epilogue = EPI_BIAS_LRELU if L.lrelu else EPI_BIAS
-        d.slope = self.SLOPE
-        d.out_fp32 = 0
-        d.split_k = 1
-        d.tile_hint, d.tile_px = self.c.TILE_HINT, self.c.TILE_PX
+            d = igemm_desc(a_in.N, L.Hout, L.Wout, L.stride, L.K, L.K, L.Cin, L.Cout, a_in, a_in.interior_off(L.pad), a_out)
+        c = self.c
+        d.epilogue, d.slope, d.split_k = (EPI_BIAS_LRELU if L.lrelu else EPI_BIAS), self.SLOPE, 1
+        d.tile_hint, d.tile_px = c.TILE_HINT, c.TILE_PX
         return d
+
+    def _dgrad_desc(self, L: Layer, g: Act, N: int, gp: Act, out_mul: int = 1) -> IgemmDesc:
+        """data gradient of conv layer L into gp: a stride-1 conv of its (zero-stuffed, for stride 2) output gradient g with the flipped panel, over L's input grid"""
+        d = igemm_desc(N, L.Hin, L.Win, 1, L.K, L.K, L.Cout, L.Cin, g, g.interior_off(L.K - 1 - L.pad), gp, out_mul=out_mul)
+        d.slope, d.split_k = self.SLOPE, 1
+        return d
+
+    @staticmethod
+    def _stem_ok(L: Layer) -> bool:
+        """the dedicated stem kernels apply to this layer (each site adds what else it needs)"""
+        return L.kind == "conv" and L.first and stem_tiles_ok(L.Cout, L.Hout, L.Wout)
+
+    def _stem_fwd_ok(self, L: Layer, y: Act) -> bool:
+        return self.c.STEM_KERNEL and self._stem_ok(L) and y.C == 64 and L.bias.dtype == torch.float32
 
     @staticmethod
     def _pool_fusable(L: Layer) -> bool:
@@ -416,6 +423,41 @@ class Plan:
         return bool(self.c.SMALL_SPLIT and not L.first and tiles < 64 and L.K * L.K * L.Cin >= 2304 and L.Cin % 64 == 0)
 
     # ------------------------------------------------------------------ forward
+    def _bind_input(self, x, train: bool, u8_size):
+        """the workspace of this call with every conv operand fresh and the input in ws["in"] -> (key, ws, x, stem_f32); stem_f32: nothing was
+        converted, the stem kernel reads the fp32 batch x itself"""
+        from .augment import U8Batch
+        N, dev = x.shape[0], x.device
+        batch = isinstance(x, U8Batch)
+        u8 = batch or u8_size is not None
+        if not batch:
+            x = x.detach()
+        if not u8:
+            if x.dim() != 4 or x.shape[1] != self.in_channels:
+                raise RuntimeError(f"expected input of shape (N, {self.in_channels}, H, W), got {tuple(x.shape)}")
+            if x.dtype != torch.float32 or not x.is_contiguous():
+                x = x.float().contiguous()
+        key, ws = self._workspace(N, x.shape if (batch or not u8) else (N, 3, u8_size[0], u8_size[1]), dev, train)
+        self._pack_all(train)
+        a = ws["in"]
+        nhwc4 = a.C == 4 and a.halo == 3
+        if u8 and not nhwc4:
+            raise ValueError("uint8 input needs a plan that starts with the 7x7/s2 stem")
+        if batch:
+            x.into_act(a)
+        elif u8:
+            from . import preprocess as _pp
+            _pp.preprocess_u8_into(x, u8_size, a)
+        else:
+            # inference: the stem kernel reads the caller's NCHW fp32 batch itself (the patch is converted on its way into LDS); training
+            # keeps the NHWC4 copy, which the stem's weight gradient reads
+            L0 = self.layers[0]
+            if (not train and self.c.STEM_F32_INPUT and nhwc4 and self._stem_fwd_ok(L0, ws["acts"][0])
+                    and 2 * L0.Hout == x.shape[2] and 2 * L0.Wout == x.shape[3]):
+                return key, ws, x, True
+            check(RT.lib().yolo_nchw_f32_to_nhwc_bf16(ptr(x), N, x.shape[1], x.shape[2], x.shape[3], a.p, a.C, a.halo, a.halo, RT.stream()), "nchw->nhwc")
+        return key, ws, x, False
+
     @_hip.device_guard
     def forward(self, x: torch.Tensor, train: bool, drop_training: bool, u8_size=None):
         """x: NCHW fp32 device tensor -- or, with ``u8_size = (H, W)``, decoded uint8 images [N][h][w][3] that
@@ -423,198 +465,150 @@ class Plan:
         ``x`` may also be a ``yolo.augment.U8Batch`` (decoded images of different sizes + their crop / colour parameters, in training too: the
         stem's weight gradient reads the same NHWC4 buffer): yolo_augment_u8 fills the stem's input buffer.
         Returns (out, saved) -- out is (N, O) fp32 if the plan ends with an fc layer, else NCHW fp32 features."""
-        from .augment import U8Batch
-        L_ = RT.lib()
-        st = RT.stream()
-        N = x.shape[0]
-        dev = x.device
-        stem_f32 = False
-        if isinstance(x, U8Batch):
-            key, ws = self._workspace(N, x.shape, dev, train)
-            self._pack_all(train)
-            a = ws["in"]
-            if not (a.C == 4 and a.halo == 3):
-                raise ValueError("uint8 input needs a plan that starts with the 7x7/s2 stem")
-            x.into_act(a)
-        elif u8_size is not None:
-            x = x.detach()
-            from . import preprocess as _pp
-            key, ws = self._workspace(N, (N, 3, u8_size[0], u8_size[1]), dev, train)
-            self._pack_all(train)
-            a = ws["in"]
-            if not (a.C == 4 and a.halo == 3):
-                raise ValueError("uint8 input needs a plan that starts with the 7x7/s2 stem")
-            _pp.preprocess_u8_into(x, u8_size, a)
-        else:
-            x = x.detach()
-            if x.dim() != 4 or x.shape[1] != self.in_channels:
-                raise RuntimeError(f"expected input of shape (N, {self.in_channels}, H, W), got {tuple(x.shape)}")
-            if x.dtype != torch.float32 or not x.is_contiguous():
-                x = x.float().contiguous()
-            key, ws = self._workspace(N, x.shape, dev, train)
-            self._pack_all(train)
-            a = ws["in"]
-            L0 = self.layers[0]
-            # inference: the stem kernel reads the caller's NCHW fp32 batch itself (the patch is converted on its way into LDS); training
-            # keeps the NHWC4 copy, which the stem's weight gradient reads
-            stem_f32 = (not train and self.c.STEM_F32_INPUT and self.c.STEM_KERNEL and a.C == 4 and a.halo == 3 and L0.kind == "conv" and L0.first and L0.Cout == 64
-                        and L0.Hout % 8 == 0 and L0.Wout % 16 == 0 and 2 * L0.Hout == x.shape[2] and 2 * L0.Wout == x.shape[3]
-                        and ws["acts"][0].C == 64 and L0.bias.dtype == torch.float32)      # = the conditions of the stem-kernel branch below
-            if stem_f32:
-                pass
-            elif a.C == 4 and a.halo == 3:
-                check(L_.yolo_nchw_f32_to_nhwc_bf16(ptr(x), N, x.shape[1], x.shape[2], x.shape[3], a.p, 4, 3, 3, st), "nchw->nhwc4")
-            else:
-                check(L_.yolo_nchw_f32_to_nhwc_bf16(ptr(x), N, x.shape[1], x.shape[2], x.shape[3], a.p, a.C, 1, 1, st), "nchw->nhwc")
-        cur = a
-        fc_saved = {}
-        out = None
-        skip_pool = False
+        N, dev = x.shape[0], x.device
+        key, ws, x, stem_f32 = self._bind_input(x, train, u8_size)
         # training, conv -> LeakyReLU -> MaxPool2d(2,2): the fused epilogue stores the pooled map and, per pooled element, the 2-bit
         # window position of the maximum; the backward pass needs nothing else of the un-pooled activation (debug_keep: the tests'
-        # teacher-forced checks read that activation, so it is written instead)
+        # teacher-forced checks read that activation, so it is written instead; debug_keep = "codes": keep the workspace of the product path)
+        f = _Pass(ws=ws, acts=ws["acts"], c=self.c, N=N, dev=dev, lib=RT.lib(), st=RT.stream(), train=train, drop_training=drop_training, x32=x if stem_f32 else None,
+                  codes_mode=train and self.c.POOL_CODES and self.debug_keep is not True, cur=ws["in"], hwc=None, fc_saved={}, out=None)
         self.grad_norm_sq.clear()
-        hwc = None
-        codes_mode = train and self.c.POOL_CODES and self.debug_keep is not True      # (debug_keep = "codes": keep the workspace of the product path)
         ws["codes"] = set()
-        for li, L in enumerate(self.layers):
-            nxt = ws["acts"][li]
-            if L.kind == "conv":
-                wf, _ = self._pack(li, train)
-                # inference: conv -> LeakyReLU -> MaxPool2d(2,2) as ONE launch when the conv output tiles into
-                # 8 x 16 pixel patches (the first two layers: 224^2 and 112^2); training keeps the un-pooled
-                # activation, which the backward pass needs
-                fuse = (not train and self.c.FUSE_POOL and li + 1 < len(self.layers) and self.layers[li + 1].kind == "pool"
-                        and self._pool_fusable(L) and not self._few_tiles(L, N))
-                if fuse:
-                    nxt = ws["acts"][li + 1]
-                d = self._conv_desc(L, cur, nxt)
-                d.pool2 = 1 if fuse else 0
-                b = L.bias.detach()
-                if L.first and self.c.STEM_KERNEL and L.Cout == 64 and L.Hout % 8 == 0 and L.Wout % 16 == 0 and nxt.C == 64 and b.dtype == torch.float32:
-                    # dedicated stem kernel: input patch staged once per 8x16 tile, weights in registers; in training the
-                    # following MaxPool2d is fused as well, with the un-pooled activation written next to the pooled one
-                    dual = (train and self.c.FUSE_POOL and li + 1 < len(self.layers) and self.layers[li + 1].kind == "pool")
-                    full = nxt if dual else None
-                    dst = ws["acts"][li + 1] if dual else nxt
-                    codes = self._codes(ws, li, dst) if (dual and codes_mode) else None
-                    with _timed(f"conv{li}" + ("+pool" if (fuse or dual) else ""), "stem", 2.0 * N * L.Hout * L.Wout * L.Cout * L.Cin * L.K * L.K):
-                        if stem_f32 and li == 0:
-                            check(L_.yolo_conv_stem7_fwd_f32(ptr(x), ptr(wf), ptr(b), N, x.shape[2], x.shape[3], self.SLOPE if L.lrelu else 1.0,
-                                                             1 if fuse else 0, dst.p, dst.img_stride, dst.row_stride, dst.interior_off(), None, 0, 0, 0, st),
-                                  "conv_stem7_fwd_f32")
-                        elif codes is not None:       # pooled map + arg-max codes: the 411 MB un-pooled activation (batch 64) is never written
-                            check(L_.yolo_conv_stem7_fwd(cur.p, ptr(wf), ptr(b), N, L.Hout, L.Wout, cur.img_stride, cur.row_stride,
-                                                         self.SLOPE if L.lrelu else 1.0, 3, dst.p, dst.img_stride, dst.row_stride,
-                                                         dst.interior_off(), ptr(codes), 0, 0, 0, st), "conv_stem7_fwd")
-                        else:
-                            check(L_.yolo_conv_stem7_fwd(cur.p, ptr(wf), ptr(b), N, L.Hout, L.Wout, cur.img_stride, cur.row_stride,
-                                                         self.SLOPE if L.lrelu else 1.0, 1 if (fuse or dual) else 0, dst.p, dst.img_stride, dst.row_stride,
-                                                         dst.interior_off(), full.p if dual else None, full.img_stride if dual else 0,
-                                                         full.row_stride if dual else 0, full.interior_off() if dual else 0, st), "conv_stem7_fwd")
-                    cur = dst
-                    skip_pool = fuse or dual
-                    continue
-                # training: the same fused pool, with the un-pooled activation written too (pool2 = 2)
-                dual = (train and self.c.FUSE_POOL and not fuse and li + 1 < len(self.layers) and self.layers[li + 1].kind == "pool"
-                        and self._pool_fusable(L) and not L.first)
-                if dual:
-                    full, pooled = nxt, ws["acts"][li + 1]
-                    d = self._conv_desc(L, cur, pooled)
-                    codes = self._codes(ws, li, pooled) if codes_mode else None
-                    if codes is not None:
-                        d.pool2 = 3
-                        auxp = ptr(codes)
-                    else:
-                        d.pool2 = 2
-                        d.aux_img_stride, d.aux_row_stride, d.aux_px_stride, d.aux_off = full.img_stride, full.row_stride, full.px_stride, full.interior_off()
-                        auxp = full.p
-                    with _timed(f"conv{li}+pool", "igemm", 2.0 * N * L.Hout * L.Wout * L.Cout * L.Cin * L.K * L.K):
-                        igemm_call(d, cur.p, ptr(wf), ptr(b), auxp, pooled.p, st, f"igemm conv{li}")
-                    cur = pooled
-                    skip_pool = True
-                    continue
-                with _timed(f"conv{li}" + ("+pool" if fuse else ""), "igemm", 2.0 * N * L.Hout * L.Wout * L.Cout * L.Cin * L.K * L.K):
-                    igemm_call(d, cur.p, ptr(wf), ptr(b), None, nxt.p, st, f"igemm conv{li}")
-                cur = nxt
-                skip_pool = fuse
-            elif L.kind == "pool" and skip_pool:
-                skip_pool = False
-            elif L.kind == "pool":
-                pd = PoolDesc(N, cur.H, cur.W, cur.C, cur.halo, nxt.halo)
-                with _timed(f"pool{li}", "maxpool2_fwd"):
-                    check(L_.yolo_maxpool2_fwd(ctypes.byref(pd), cur.p, nxt.p, st), "maxpool")
-                cur = nxt
-            elif L.kind == "flatten":
-                if not train and isinstance(cur, Act) and cur.halo == 0 and cur.halo_hi == 0 and self.c.FLATTEN_FREE:
-                    hwc = (cur.C, cur.H * cur.W)            # the next Linear layer takes (hw, c)-ordered panels
-                    cur = cur.t.view(N, -1)
-                    continue
-                check(L_.yolo_nhwc_bf16_to_nchw_bf16(cur.p, N, cur.C, cur.H, cur.W, cur.halo, ptr(nxt), st), "flatten")
-                cur = nxt
-            elif L.kind == "fc":
-                self.params_ready.wait(dev)      # yolo.optim.Adam(overlap): the Linear layers' update of the last step runs on a second stream
-                if train:
-                    wf, _ = self._pack(li, False)
-                else:
-                    wf = self._pack_fc_blocked(li, hwc)
-                    hwc = None
-                xin = cur  # (N, K) bf16
-                K = L.Cin
-                d = IgemmDesc()
-                d.N, d.Ho, d.Wo = N, 1, 1
-                d.in_img_stride, d.in_row_stride, d.in_px_stride, d.in_off = xin.shape[1], 0, xin.shape[1], 0
-                d.stride, d.KH, d.KW, d.tap_len, d.Cout = 1, 1, 1, K, L.Cout
-                d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = L.Cout, 0, L.Cout, 0
-                d.slope = self.SLOPE
-                d.out_fp32 = 1
-                d.w_blocked = 0 if train else 1
-                last = (li == len(self.layers) - 1)
-                nk = K // 64
-                # blocked panels (inference) run the 3-stage weight-stream kernel: 32 co-tiles x 32 splits = two full rounds of 512 slots
-                splits = max(1, min(32 if d.w_blocked else 48, nk // 16)) if K >= 4096 else 1
-                b = L.bias.detach()
-                if splits > 1:
-                    # every K split STORES its partial [N][Cout] result as a slab; the finishing pass adds the slabs in fixed
-                    # order -> the forward is bit-reproducible (fp32 atomics of 32 splits were not) and needs no zero fill
-                    acc = RT._splitk_scratch(splits * N * L.Cout, zero=False)
-                    d.epilogue, d.split_k, d.split_slabs = EPI_NONE, splits, 1
-                    with _timed(f"fc{li}", "igemm", 2.0 * N * L.Cout * L.Cin):
-                        _igemm(L_, d, ptr(xin), ptr(wf), None, None, ptr(acc), st, f"igemm fc{li}")
-                    yb = torch.empty((N, L.Cout), dtype=torch.bfloat16, device=dev) if not last else None
-                    yf = torch.empty((N, L.Cout), dtype=torch.float32, device=dev) if last else None
-                    check(L_.yolo_bias_lrelu_rows_slabs(ptr(acc), splits, ptr(b), N, L.Cout, self.SLOPE if L.lrelu else 1.0, ptr(yb), ptr(yf), st),
-                          "bias_lrelu_rows")
-                else:
-                    yf = torch.empty((N, L.Cout), dtype=torch.float32, device=dev)
-                    d.epilogue, d.split_k = (EPI_BIAS_LRELU if L.lrelu else EPI_BIAS), 1
-                    with _timed(f"fc{li}", "igemm", 2.0 * N * L.Cout * L.Cin):
-                        _igemm(L_, d, ptr(xin), ptr(wf), ptr(b), None, ptr(yf), st, f"igemm fc{li}")
-                    yb = None
-                    if not last:
-                        yb = torch.empty((N, L.Cout), dtype=torch.bfloat16, device=dev)
-                        check(L_.yolo_cast_f32_to_bf16(ptr(yf), yf.numel(), ptr(yb), st), "cast")
-                mask = None
-                y_act = yb
-                if L.drop_mod is not None:
-                    L.dropout = float(L.drop_mod.p)          # (the backward of this forward reads L.dropout)
-                if not last and L.dropout > 0 and drop_training:
-                    mask = (torch.rand((N, L.Cout), device=dev) >= L.dropout).to(torch.uint8)
-                    yd = torch.empty_like(yb)
-                    check(L_.yolo_dropout_bf16(ptr(yb), ptr(mask), 1.0 / max(1.0 - L.dropout, 1e-12) if L.dropout < 1.0 else 0.0, yb.numel(), ptr(yd), st), "dropout")
-                    cur = yd
-                else:
-                    cur = yb
-                fc_saved[li] = (xin, y_act, mask)
-                if last:
-                    out = yf
+        step = {"conv": self._fwd_conv, "pool": self._fwd_pool, "flatten": self._fwd_flatten, "fc": self._fwd_fc}
+        li = 0
+        while li < len(self.layers):
+            li += step[self.layers[li].kind](f, li)       # (a conv that pools consumes the MaxPool2d behind it)
+        out, cur = f.out, f.cur
         if out is None:
             out = torch.empty((N, cur.C, cur.H, cur.W), dtype=torch.float32, device=dev)
-            check(L_.yolo_nhwc_bf16_to_nchw_f32(cur.p, N, cur.C, cur.H, cur.W, cur.halo, ptr(out), st), "nhwc->nchw")
-        saved = (key, ws, fc_saved, N, dev) if train else None
-        if not train:
-            self._release(key, ws)
-        return out, saved
+            check(f.lib.yolo_nhwc_bf16_to_nchw_f32(cur.p, N, cur.C, cur.H, cur.W, cur.halo, ptr(out), f.st), "nhwc->nchw")
+        if train:
+            return out, (key, ws, f.fc_saved, N, dev)
+        self._release(key, ws)
+        return out, None
+
+    def _fwd_conv(self, f, li: int) -> int:
+        """conv (+ LeakyReLU), with the MaxPool2d(2,2) behind it where it fuses -> layers consumed.  Inference folds the pool into the epilogue
+        (``fuse``, pool2 = 1: the conv output tiles into 8 x 16 pixel patches or whole row pairs); training does too (``dual``) and keeps what the
+        backward pass needs: arg-max codes (pool2 = 3), or the un-pooled activation next to the pooled one (pool2 = 2)"""
+        L, N, train, acts, cur = self.layers[li], f.N, f.train, f.acts, f.cur
+        wf, _ = self._pack(li, train)
+        pool_next = f.c.FUSE_POOL and li + 1 < len(self.layers) and self.layers[li + 1].kind == "pool"
+        fuse = not train and pool_next and self._pool_fusable(L) and not self._few_tiles(L, N)
+        b = L.bias.detach()
+        full = acts[li]
+        if L.first and self._stem_fwd_ok(L, full):
+            return self._fwd_stem(f, li, wf, b, fuse, train and pool_next)
+        dual = train and pool_next and self._pool_fusable(L) and not L.first
+        dst = acts[li + 1] if (fuse or dual) else full
+        d = self._conv_desc(L, cur, dst)
+        d.pool2, aux = (1 if fuse else 0), None
+        if dual:
+            codes = self._codes(f.ws, li, dst) if f.codes_mode else None
+            if codes is not None:
+                d.pool2, aux = 3, ptr(codes)
+            else:
+                d.pool2, aux = 2, full.p
+                desc_aux(d, full)
+        with _timed(f"conv{li}" + ("+pool" if (fuse or dual) else ""), "igemm", 2.0 * N * L.Hout * L.Wout * L.Cout * L.Cin * L.K * L.K):
+            igemm_call(d, cur.p, ptr(wf), ptr(b), aux, dst.p, f.st, f"igemm conv{li}")
+        f.cur = dst
+        return 2 if (fuse or dual) else 1
+
+    def _fwd_stem(self, f, li: int, wf, b, fuse: bool, dual: bool) -> int:
+        """dedicated stem kernel: input patch staged once per 8x16 tile, weights in registers.  Second output: the pool's arg-max codes (the 411 MB
+        un-pooled activation of batch 64 is never written), or that activation next to the pooled one (training without codes), or none"""
+        L, N, cur = self.layers[li], f.N, f.cur
+        full = f.ws["acts"][li]
+        dst = f.ws["acts"][li + 1] if (fuse or dual) else full
+        codes = self._codes(f.ws, li, dst) if (dual and f.codes_mode) else None
+        slope = self.SLOPE if L.lrelu else 1.0
+        if codes is not None:
+            pool2, second = 3, (ptr(codes), 0, 0, 0)
+        elif dual:
+            pool2, second = 1, (full.p, full.img_stride, full.row_stride, full.interior_off())
+        else:
+            pool2, second = (1 if fuse else 0), (None, 0, 0, 0)
+        out = (dst.p, dst.img_stride, dst.row_stride, dst.interior_off())
+        with _timed(f"conv{li}" + ("+pool" if (fuse or dual) else ""), "stem", 2.0 * N * L.Hout * L.Wout * L.Cout * L.Cin * L.K * L.K):
+            if f.x32 is not None and li == 0:
+                x = f.x32
+                check(f.lib.yolo_conv_stem7_fwd_f32(ptr(x), ptr(wf), ptr(b), N, x.shape[2], x.shape[3], slope, pool2, *out, *second, f.st), "conv_stem7_fwd_f32")
+            else:
+                check(f.lib.yolo_conv_stem7_fwd(cur.p, ptr(wf), ptr(b), N, L.Hout, L.Wout, cur.img_stride, cur.row_stride, slope, pool2, *out, *second, f.st),
+                      "conv_stem7_fwd")
+        f.cur = dst
+        return 2 if (fuse or dual) else 1
+
+    def _fwd_pool(self, f, li: int) -> int:
+        cur, nxt = f.cur, f.ws["acts"][li]
+        pd = PoolDesc(f.N, cur.H, cur.W, cur.C, cur.halo, nxt.halo)
+        with _timed(f"pool{li}", "maxpool2_fwd"):
+            check(f.lib.yolo_maxpool2_fwd(ctypes.byref(pd), cur.p, nxt.p, f.st), "maxpool")
+        f.cur = nxt
+        return 1
+
+    def _fwd_flatten(self, f, li: int) -> int:
+        cur = f.cur
+        if not f.train and isinstance(cur, Act) and cur.halo == 0 and cur.halo_hi == 0 and self.c.FLATTEN_FREE:
+            f.hwc = (cur.C, cur.H * cur.W)            # the next Linear layer takes (hw, c)-ordered panels
+            f.cur = cur.t.view(f.N, -1)
+            return 1
+        nxt = f.ws["acts"][li]
+        check(f.lib.yolo_nhwc_bf16_to_nchw_bf16(cur.p, f.N, cur.C, cur.H, cur.W, cur.halo, ptr(nxt), f.st), "flatten")
+        f.cur = nxt
+        return 1
+
+    def _fwd_fc(self, f, li: int) -> int:
+        L, N, dev, L_, st = self.layers[li], f.N, f.dev, f.lib, f.st
+        self.params_ready.wait(dev)      # yolo.optim.Adam(overlap): the Linear layers' update of the last step runs on a second stream
+        if f.train:
+            wf, _ = self._pack(li, False)
+        else:
+            wf = self._pack_fc_blocked(li, f.hwc)
+            f.hwc = None
+        xin = f.cur  # (N, K) bf16
+        K = L.Cin
+        d = rows_desc(N, xin.shape[1], K, L.Cout)
+        d.slope, d.out_fp32 = self.SLOPE, 1
+        d.w_blocked = 0 if f.train else 1
+        last = (li == len(self.layers) - 1)
+        nk = K // 64
+        # blocked panels (inference) run the 3-stage weight-stream kernel: 32 co-tiles x 32 splits = two full rounds of 512 slots
+        splits = max(1, min(32 if d.w_blocked else 48, nk // 16)) if K >= 4096 else 1
+        b = L.bias.detach()
+        if splits > 1:
+            # every K split STORES its partial [N][Cout] result as a slab; the finishing pass adds the slabs in fixed
+            # order -> the forward is bit-reproducible (fp32 atomics of 32 splits were not) and needs no zero fill
+            acc = RT._splitk_scratch(splits * N * L.Cout, zero=False)
+            d.epilogue, d.split_k, d.split_slabs = EPI_NONE, splits, 1
+            with _timed(f"fc{li}", "igemm", 2.0 * N * L.Cout * L.Cin):
+                _igemm(L_, d, ptr(xin), ptr(wf), None, None, ptr(acc), st, f"igemm fc{li}")
+            yb = torch.empty((N, L.Cout), dtype=torch.bfloat16, device=dev) if not last else None
+            yf = torch.empty((N, L.Cout), dtype=torch.float32, device=dev) if last else None
+            check(L_.yolo_bias_lrelu_rows_slabs(ptr(acc), splits, ptr(b), N, L.Cout, self.SLOPE if L.lrelu else 1.0, ptr(yb), ptr(yf), st),
+                  "bias_lrelu_rows")
+        else:
+            yf = torch.empty((N, L.Cout), dtype=torch.float32, device=dev)
+            d.epilogue, d.split_k = (EPI_BIAS_LRELU if L.lrelu else EPI_BIAS), 1
+            with _timed(f"fc{li}", "igemm", 2.0 * N * L.Cout * L.Cin):
+                _igemm(L_, d, ptr(xin), ptr(wf), ptr(b), None, ptr(yf), st, f"igemm fc{li}")
+            yb = None
+            if not last:
+                yb = torch.empty((N, L.Cout), dtype=torch.bfloat16, device=dev)
+                check(L_.yolo_cast_f32_to_bf16(ptr(yf), yf.numel(), ptr(yb), st), "cast")
+        mask = None
+        if L.drop_mod is not None:
+            L.dropout = float(L.drop_mod.p)          # (the backward of this forward reads L.dropout)
+        f.cur = yb
+        if not last and L.dropout > 0 and f.drop_training:
+            mask = (torch.rand((N, L.Cout), device=dev) >= L.dropout).to(torch.uint8)
+            f.cur = torch.empty_like(yb)
+            check(L_.yolo_dropout_bf16(ptr(yb), ptr(mask), 1.0 / max(1.0 - L.dropout, 1e-12) if L.dropout < 1.0 else 0.0, yb.numel(), ptr(f.cur), st), "dropout")
+        f.fc_saved[li] = (xin, yb, mask)
+        if last:
+            f.out = yf
+        return 1
 
     # ------------------------------------------------------------------ backward
     @staticmethod
@@ -626,6 +620,14 @@ class Plan:
             ws["misc"][("codes", li)] = c
         ws["codes"].add(li)
         return c
+
+    @staticmethod
+    def _misc(ws, key, make):
+        """a buffer of the workspace that the first pass needing it allocates"""
+        buf = ws["misc"].get(key)
+        if buf is None:
+            buf = ws["misc"][key] = make()
+        return buf
 
     def _grad_buf(self, ws, li: int, N, dev) -> Act:
         """gradient wrt the (post-activation-derivative) output of conv layer li, in the geometry
@@ -639,12 +641,6 @@ class Plan:
                 g = Act(N, L.Hin, L.Win, L.Cout, 1, dev)
             ws["grads"][li] = g
         return g
-
-    def _grad_out_strides(self, L: Layer, g: Act):
-        """(img, row, px, off) strides a producer uses to write layer L's output gradient into g."""
-        if L.stride == 1 or L.first:
-            return g.img_stride, g.row_stride, g.px_stride, g.interior_off()
-        return g.img_stride, 2 * g.row_stride, 2 * g.px_stride, g.interior_off()
 
     @staticmethod
     def _wgrad_desc(L: Layer, g: Act, xin: Act, N: int) -> WgradDesc:
@@ -676,367 +672,271 @@ class Plan:
 
     def backward(self, saved, gout: torch.Tensor, need_gx: bool):
         """gout: gradient of the plan output (same shape as forward's out).  Returns (gx or None, [param grads])."""
-        L_ = RT.lib()
-        st = RT.stream()
-        key, ws, fc_saved, N, dev = saved
-        self._apply_geom(ws)
-        if self.arena is not None:
-            self.arena[self._arena_w_end:].zero_()      # bias gradients are accumulated with atomics
-        grads: dict[int, tuple] = {}
-        nl = len(self.layers)
-        # two zero-filled fp32 scratch areas for the whole pass: the packed conv weight gradients (targets of yolo_wgrad's atomics; a buffer
-        # of the workspace, cleared ON THE SIDE STREAM, where its first user runs: 80 MB of fill off the data-gradient chain) and,
-        # without an arena, the bias gradients (fresh every pass: they are handed to autograd) -- two fills instead of ~50
-        offs, tot = {}, 0
-        for i, L in enumerate(self.layers):
-            if L.kind == "conv":
-                offs[("w", i)] = tot
-                tot += _round_up(L.Cout * 7 * 8 * 4 if L.first else L.Cout * L.K * L.K * L.Cin, 64)
-        btot = 0
-        if self.arena is None:
-            for i, L in enumerate(self.layers):
-                if L.kind in ("conv", "fc"):
-                    offs[("b", i)] = btot
-                    btot += _round_up(L.Cout, 64)
-        scratch = ws["misc"].get("wgrad_scratch")
-        if scratch is None or scratch.numel() < tot:
-            scratch = ws["misc"]["wgrad_scratch"] = torch.empty(max(tot, 1), dtype=torch.float32, device=dev)
-        bscratch = torch.zeros(max(btot, 1), dtype=torch.float32, device=dev)
-
-        def grad_tensors(i):
-            L = self.layers[i]
-            if self.arena is not None:
-                dw, db, _, _ = self.arena_views[i]
-                return dw, db
-            o = offs[("b", i)]
-            return torch.empty_like(L.weight, dtype=torch.float32), bscratch[o: o + L.Cout]
-
-        # packed -> OIHW conversion of finished conv gradients is deferred and done for several layers per
-        # launch (yolo_unpack_conv_wgrads_multi); gradients become final (and are announced) at the flush
-        pending: list[tuple] = []
-        stem_dpool = None            # pooled gradient handed straight to the stem's weight-gradient kernel (pool backward fused there)
-
-        def flush():
-            items = [ConvUnpackItem(dwp.data_ptr(), dw.data_ptr(), L.Cout, L.Cin, L.K, L.K) for (i, L, dwp, dw) in pending if self._multi_ok(L)]
-            if items:
-                check(L_.yolo_unpack_conv_wgrads_multi((ConvUnpackItem * len(items))(*items), len(items), RT.stream()), "unpack_conv_wgrads_multi")
-            for (i, L, dwp, dw) in pending:
-                if not self._multi_ok(L):
-                    if L.first:
-                        check(L_.yolo_unpack_conv_wgrad(ptr(dwp), L.Cout, 3, 7, 7, 4, 8, ptr(dw), 0, RT.stream()), "unpack")
-                    else:
-                        check(L_.yolo_unpack_conv_wgrad(ptr(dwp), L.Cout, L.Cin, L.K, L.K, L.Cin, L.K, ptr(dw), 0, RT.stream()), "unpack")
-                self._layer_done(i)
-            pending.clear()
-
+        b = _Backward(self, saved, need_gx)
         gout = gout.detach()
         if gout.dtype != torch.float32 or not gout.is_contiguous():
             gout = gout.float().contiguous()
+        with b.on_side():
+            b.scratch.zero_()
+        li = len(self.layers) - 1
+        self._bwd_seed(b, li, gout)
+        step = {"fc": self._bwd_fc, "pool": self._bwd_pool, "conv": self._bwd_conv}
+        while li >= 0:
+            assert self.layers[li].kind != "flatten", "nn.Flatten is handled together with the Linear layer behind it"
+            li -= step[self.layers[li].kind](b, li)       # (the Linear behind nn.Flatten consumes both)
+        return self._finish_backward(b)
 
+    def _bwd_seed(self, b, li: int, gout: torch.Tensor):
+        """the gradient flowing into the last layer li: b.g_flat, fp32 (N, K) rows wrt an fc layer's output, or b.g_act, an Act wrt a conv / pool
+        output (already through LeakyReLU')"""
+        L, N, dev = self.layers[li], b.N, b.dev
+        if L.kind == "fc":
+            b.g_flat = gout.reshape(N, -1)
+            return
+        # plan ends with feature maps (NCHW fp32 gradient): last layer is a conv(+lrelu) or a pool
+        y = b.ws["acts"][li]
+        graw = Act(N, y.H, y.W, y.C, 1, dev)
+        check(b.lib.yolo_nchw_f32_to_nhwc_bf16(ptr(gout), N, y.C, y.H, y.W, graw.p, y.C, 1, 1, b.st), "gout->nhwc")
+        if L.kind == "conv":
+            b.g_act = self._grad_buf(b.ws, li, N, dev)
+            self._apply_dlrelu_into(graw, y, L, b.g_act, b.st)
+        else:
+            assert L.kind == "pool", "plans end with fc, conv or pool"
+            b.g_act = graw
+
+    def _bwd_fc(self, b, li: int) -> int:
+        L, N, dev, L_, st, det = self.layers[li], b.N, b.dev, b.lib, b.st, b.det
+        xin, y_act, mask = b.fc_saved[li]
+        last = (li == len(self.layers) - 1)
+        ldg = _round_up(L.Cout, 32)
+        gb = torch.empty((N, ldg), dtype=torch.bfloat16, device=dev)
+        # through dropout + LeakyReLU of THIS layer's output (none for the last layer)
+        check(L_.yolo_scale_rows_to_bf16(ptr(b.g_flat), ptr(mask), ((1.0 / (1.0 - L.dropout)) if L.dropout < 1.0 else 0.0) if mask is not None else 1.0,
+                                         ptr(y_act) if (L.lrelu and not last) else None, self.SLOPE, N, L.Cout, ldg, ptr(gb), st), "scale_rows")
+        # weight / bias gradient, native [O][K] layout
+        dw, db = b.grad_tensors(li)
+        wd = WgradDesc(N, ldg, L.Cin, L.Cout, L.Cin, 1, 1, 0, 0, 1, 0)
+        nsq = None
+        if det:
+            pass      # the norm hint ends in one fp64 atomic per workgroup: the optimizer's order-fixed pass reads this gradient instead
+        elif L.Cout * L.Cin >= self.c.FC_NORM_IN_WGRAD and L.Cin % 4 == 0:
+            # the kernel that stores this gradient also sums its squares: the optimizer's global-norm pass (clip_grad_norm_) then
+            # need not read the 822 MB of the Linear behind nn.Flatten again (yolo.optim.grad_norm_sq, `known`)
+            nsq = torch.zeros((), dtype=torch.float64, device=dev)
+            wd.dw_sumsq = nsq.data_ptr()
+        # HBM-bound both: the weight gradient of the Linear behind nn.Flatten STORES 822 MB (4.1 TB/s alone), its data gradient READS
+        # the 411 MB of weights (2.7 TB/s alone); side by side they share the memory system instead of taking turns
+        side = self.c.FC_WGRAD_SIDE and b.side_t is not None
+        if side:
+            b.fc_keep.append(gb)          # (a temporary of the main stream's allocator that the second stream reads: alive until the streams join)
+        with b.on_side(side) as wst:
+            if det:
+                _attach_wgrad_slabs(L_, wd, dev, wst)
+            with _timed(f"fc{li}.wgrad", "wgrad", 2.0 * N * L.Cout * L.Cin):
+                check(L_.yolo_wgrad(ctypes.byref(wd), ptr(xin), ptr(gb), ptr(dw), ptr(db), wst), f"wgrad fc{li}")
+            self._layer_done(li)
+        if nsq is not None:
+            # (no reference to dw itself: autograd takes the gradient over without a copy only while nobody else holds it)
+            self.grad_norm_sq[id(L.weight)] = ((dw.data_ptr(), tuple(dw.shape)), dw._version, nsq)
+        b.grads[li] = (dw, db)
+        # data gradient
+        if li == 0 and not b.need_gx:
+            return 1
+        if li >= 2 and self.layers[li - 1].kind == "flatten" and self.layers[li - 2].kind in ("conv", "pool"):
+            # the Linear behind nn.Flatten (205 M weights): reduce over the OUTPUT features with the
+            # weight-gradient kernel -- both operands are strided along the reduction axis there, which
+            # is exactly how W[o][k] and g^T[o][n] lie in memory -- and read the forward bf16 copy of W:
+            #   dxT[k][n] = sum_o W[o][k] * gT[o][n]
+            Lc = self.layers[li - 2]
+            y = b.ws["acts"][li - 2]
+            wf, _ = self._pack(li, False)
+            ldn = _round_up(N, 8)
+            gT = torch.zeros((L.Cout, ldn), dtype=torch.bfloat16, device=dev)
+            check(L_.yolo_transpose_bf16(ptr(gb), N, L.Cout, ldg, ptr(gT), ldn, st), "transpose g")
+            dxT = torch.zeros((L.Cin, N), dtype=torch.float32, device=dev)
+            wd = WgradDesc(L.Cout, L.Cin, ldn, L.Cin, N, 1, 1, 0, 0, 0, 1)   # split 0: library's schedule (0.095 vs 0.135 ms with 3 ranges)
+            if det:
+                wd.accumulate = 0       # (dxT is zero: the same value) the pixel ranges of a tile as slabs, on this stream's own scratch
+                _attach_wgrad_slabs(L_, wd, dev, st)
+            with _timed(f"fc{li}.dgrad", "wgrad", 2.0 * N * L.Cout * L.Cin):
+                check(L_.yolo_wgrad(ctypes.byref(wd), ptr(gT), ptr(wf), ptr(dxT), None, st), f"dgrad fc{li}")
+            if Lc.kind == "conv":
+                assert Lc.stride == 1, "nn.Flatten is expected after a stride-1 conv or a pool"
+                g = self._grad_buf(b.ws, li - 2, N, dev)
+                yact = y.p if Lc.lrelu else None
+            else:
+                g = self._misc(b.ws, "graw_flat", lambda: Act(N, y.H, y.W, y.C, 1, dev))
+                yact = None
+            check(L_.yolo_fc_dgrad_to_nhwc(ptr(dxT), N, y.C, y.H, y.W, 1, yact, self.SLOPE, g.p, st), "fc_dgrad_to_nhwc")
+            b.g_act, b.g_flat = g, None
+            return 2          # nn.Flatten is done as well
+        _, wt = self._pack(li, True)
+        d = rows_desc(N, ldg, ldg, L.Cin)
+        d.epilogue, d.slope, d.out_fp32, d.split_k = EPI_NONE, self.SLOPE, 1, 1
+        b.g_flat = torch.empty((N, L.Cin), dtype=torch.float32, device=dev)
+        with _timed(f"fc{li}.dgrad", "igemm", 2.0 * N * L.Cout * L.Cin):
+            _igemm(L_, d, ptr(gb), ptr(wt), None, None, ptr(b.g_flat), st, f"dgrad fc{li}")
+        return 1
+
+    def _bwd_pool(self, b, li: int) -> int:
+        """b.g_act = gradient wrt the pooled output -> gradient wrt the conv in front (through its LeakyReLU)"""
+        lc, ws, g_act = li - 1, b.ws, b.g_act
+        Lc = self.layers[lc]
+        assert Lc.kind == "conv" and Lc.lrelu, "MaxPool2d is expected right after conv+LeakyReLU"
+        if lc == 0 and self.c.STEM_POOL_BWD_FUSED and self._stem_ok(Lc) and g_act.halo == 1 and not b.need_gx:
+            # the stem's weight-gradient kernel rebuilds this pool's (+ LeakyReLU's) backward per tile from the activation and the pooled
+            # gradient: the 224x224x64 gradient buffer is never written or read (a gradient wrt the input image needs it as a tensor)
+            b.stem_dpool = g_act
+            return 1
+        yfull = ws["acts"][lc]
+        g = self._grad_buf(ws, lc, b.N, b.dev)
+        pd = PoolDesc(b.N, yfull.H, yfull.W, yfull.C, 1, 1)
+        with _timed(f"pool{li}.bwd", "maxpool2_bwd"):
+            if lc in ws.get("codes", ()):
+                ypool = ws["acts"][li]
+                assert (ypool.Hp, ypool.Wp, ypool.C, ypool.halo) == (g_act.Hp, g_act.Wp, g_act.C, g_act.halo)
+                check(b.lib.yolo_maxpool2_bwd_codes(ctypes.byref(pd), ypool.p, ptr(ws["misc"][("codes", lc)]), g_act.p, self.SLOPE, g.p, b.st), "maxpool_bwd_codes")
+            else:
+                check(b.lib.yolo_maxpool2_bwd_lrelu(ctypes.byref(pd), yfull.p, g_act.p, self.SLOPE, g.p, b.st), "maxpool_bwd")
+        b.g_act = g
+        return 1
+
+    def _bwd_conv(self, b, li: int) -> int:
         # The data gradients form the chain every later layer waits for; a layer's weight gradient only needs that layer's output
         # gradient and is first read by the optimizer.  The conv weight gradients (and their unpack passes / gradient-ready
         # callbacks) therefore go to a second stream: their atomic epilogues, partial last rounds and prologues -- phases in which a
         # kernel leaves the matrix cores idle -- overlap with the data-gradient kernels of the layers below, workgroup by workgroup.
-        main_t = RT.STREAMS.current(dev)
-        side_t = self._side_stream(dev) if self.c.WGRAD_STREAM else None
-        det = bool(self.c.DETERMINISTIC)     # every yolo_wgrad launch with slabs (scratch per stream), no norm hint (EngineConfig.DETERMINISTIC)
+        g = b.g_act        # dZ of this layer, flat-geometry buffer
+        self._bwd_conv_wgrad(b, li, g)
+        if li > 0:
+            self._bwd_conv_dgrad(b, li, g)
+        return 1
 
-        def _on_side():
-            return _on_side_stream(main_t, side_t, self.on_stream_wait if self.arena is not None else None)
-
-        with _on_side():
-            scratch.zero_()
-        fc_keep: list = []
-
-        # what each layer's input activation is
-        def input_of(li):
-            return ws["in"] if li == 0 else ws["acts"][li - 1]
-
-        # g_cur: gradient flowing into the output of layer li (representation depends on kind)
-        g_flat = None       # fp32 (N, K) gradient wrt an fc layer's output / flatten output
-        g_act: Act | None = None   # Act gradient wrt a conv/pool output (already through LeakyReLU')
-        li = nl - 1
-        if self.layers[li].kind == "fc":
-            g_flat = gout.reshape(N, -1)
-        else:
-            # plan ends with feature maps (NCHW fp32 gradient): last layer is a conv(+lrelu) or a pool
-            L = self.layers[li]
-            y = ws["acts"][li]
-            graw = Act(N, y.H, y.W, y.C, 1, dev)
-            check(L_.yolo_nchw_f32_to_nhwc_bf16(ptr(gout), N, y.C, y.H, y.W, graw.p, y.C, 1, 1, st), "gout->nhwc")
-            if L.kind == "conv":
-                g = self._grad_buf(ws, li, N, dev)
-                self._apply_dlrelu_into(graw, y, L, g, st)
-                g_act = g
+    def _bwd_conv_wgrad(self, b, li: int, g: Act):
+        """weight + bias gradient of conv layer li on the second stream: the stem's direct kernels, its im2col fallback, or yolo_wgrad into the packed
+        scratch (unpacked to OIHW later, several layers per launch: b.flush)"""
+        L, N, dev, ws, L_ = self.layers[li], b.N, b.dev, b.ws, b.lib
+        xin = ws["in"] if li == 0 else ws["acts"][li - 1]
+        dw, db = b.grads[li] = b.grad_tensors(li)
+        o = b.offs[("w", li)]
+        with b.on_side() as wst:
+            if self._stem_ok(L):
+                self._bwd_stem_wgrad(b, L, g, xin, dw, db, wst)
+                b.flush()
+                self._layer_done(li)
+                return
+            if L.first:
+                xcol = self._misc(ws, "xcol", lambda: Act(N, L.Hout, L.Wout, 7 * 32, 1, dev))
+                check(L_.yolo_im2col_rows(xin.p, xin.img_stride, xin.row_stride, xin.px_stride, 2, 7, 32, N, L.Hout, L.Wout, 1, xcol.p, wst), "im2col_rows")
+                dwp = b.scratch[o: o + L.Cout * 7 * 8 * 4]
+                wd = WgradDesc(g.slots, g.px_stride, xcol.px_stride, L.Cout, 7 * 32, 1, 1, 0, xcol.row_stride, max(1, min(1024, g.slots // 4096)), 0)
+                slabs, xp, macs = b.det, xcol.p, 147
             else:
-                assert L.kind == "pool", "plans end with fc, conv or pool"
-                g_act = graw
+                dwp = b.scratch[o: o + L.Cout * L.K * L.K * L.Cin]
+                # reduce over the layer's OUTPUT pixels only (not over every slot of the zero-haloed -- for stride 2
+                # zero-stuffed -- gradient buffer, whose geometry the input buffer shares slot for slot)
+                # (measured: worth it from 28x28 down and for stride 2; at 56x56 and above the halo is < 8 % of the slots
+                # and the per-row coordinate arithmetic costs more than it saves)
+                wd = self._wgrad_desc(L, g, xin, N)
+                slabs, xp, macs = b.det or (self.c.WGRAD_SLABS and wd.variant >= 5), xin.p, L.Cin * L.K * L.K
+            if slabs:
+                _attach_wgrad_slabs(L_, wd, dev, wst)
+            with _timed(f"conv{li}.wgrad", "wgrad", 2.0 * N * L.Hout * L.Wout * L.Cout * macs):
+                check(L_.yolo_wgrad(ctypes.byref(wd), xp, g.p, ptr(dwp), ptr(db), wst), f"wgrad conv{li}")
+            b.pending.append((li, L, dwp, dw))
+            if li == 0 or sum(t[2].numel() for t in b.pending) >= (16 << 20):
+                b.flush()
 
-        while li >= 0:
-            L = self.layers[li]
-            if L.kind == "fc":
-                xin, y_act, mask = fc_saved[li]
-                last = (li == nl - 1)
-                ldg = _round_up(L.Cout, 32)
-                gb = torch.empty((N, ldg), dtype=torch.bfloat16, device=dev)
-                # through dropout + LeakyReLU of THIS layer's output (none for the last layer)
-                check(L_.yolo_scale_rows_to_bf16(ptr(g_flat), ptr(mask), ((1.0 / (1.0 - L.dropout)) if L.dropout < 1.0 else 0.0) if mask is not None else 1.0,
-                                                 ptr(y_act) if (L.lrelu and not last) else None, self.SLOPE, N, L.Cout, ldg, ptr(gb), st), "scale_rows")
-                # weight / bias gradient, native [O][K] layout
-                dw, db = grad_tensors(li)
-                wd = WgradDesc(N, ldg, L.Cin, L.Cout, L.Cin, 1, 1, 0, 0, 1, 0)
-                nsq = None
-                if det:
-                    pass      # the norm hint ends in one fp64 atomic per workgroup: the optimizer's order-fixed pass reads this gradient instead
-                elif L.Cout * L.Cin >= self.c.FC_NORM_IN_WGRAD and L.Cin % 4 == 0:
-                    # the kernel that stores this gradient also sums its squares: the optimizer's global-norm pass (clip_grad_norm_) then
-                    # need not read the 822 MB of the Linear behind nn.Flatten again (yolo.optim.grad_norm_sq, `known`)
-                    nsq = torch.zeros((), dtype=torch.float64, device=dev)
-                    wd.dw_sumsq = nsq.data_ptr()
-                if self.c.FC_WGRAD_SIDE and side_t is not None:
-                    # HBM-bound both: the weight gradient of the Linear behind nn.Flatten STORES 822 MB (4.1 TB/s alone), its data gradient READS
-                    # the 411 MB of weights (2.7 TB/s alone); side by side they share the memory system instead of taking turns
-                    fc_keep.append(gb)          # (a temporary of the main stream's allocator that the second stream reads: alive until the streams join)
-                    with _on_side() as wst:
-                        if det:
-                            _attach_wgrad_slabs(L_, wd, dev, wst)
-                        with _timed(f"fc{li}.wgrad", "wgrad", 2.0 * N * L.Cout * L.Cin):
-                            check(L_.yolo_wgrad(ctypes.byref(wd), ptr(xin), ptr(gb), ptr(dw), ptr(db), wst), f"wgrad fc{li}")
-                        self._layer_done(li)
-                else:
-                    if det:
-                        _attach_wgrad_slabs(L_, wd, dev, st)
-                    with _timed(f"fc{li}.wgrad", "wgrad", 2.0 * N * L.Cout * L.Cin):
-                        check(L_.yolo_wgrad(ctypes.byref(wd), ptr(xin), ptr(gb), ptr(dw), ptr(db), st), f"wgrad fc{li}")
-                    self._layer_done(li)
-                if nsq is not None:
-                    # (no reference to dw itself: autograd takes the gradient over without a copy only while nobody else holds it)
-                    self.grad_norm_sq[id(L.weight)] = ((dw.data_ptr(), tuple(dw.shape)), dw._version, nsq)
-                grads[li] = (dw, db)
-                # data gradient
-                need_prev = li > 0 or need_gx
-                behind_flatten = li >= 2 and self.layers[li - 1].kind == "flatten" and self.layers[li - 2].kind in ("conv", "pool")
-                if need_prev and behind_flatten:
-                    # the Linear behind nn.Flatten (205 M weights): reduce over the OUTPUT features with the
-                    # weight-gradient kernel -- both operands are strided along the reduction axis there, which
-                    # is exactly how W[o][k] and g^T[o][n] lie in memory -- and read the forward bf16 copy of W:
-                    #   dxT[k][n] = sum_o W[o][k] * gT[o][n]
-                    Lc = self.layers[li - 2]
-                    y = ws["acts"][li - 2]
-                    wf, _ = self._pack(li, False)
-                    ldn = _round_up(N, 8)
-                    gT = torch.zeros((L.Cout, ldn), dtype=torch.bfloat16, device=dev)
-                    check(L_.yolo_transpose_bf16(ptr(gb), N, L.Cout, ldg, ptr(gT), ldn, st), "transpose g")
-                    dxT = torch.zeros((L.Cin, N), dtype=torch.float32, device=dev)
-                    wd = WgradDesc(L.Cout, L.Cin, ldn, L.Cin, N, 1, 1, 0, 0, 0, 1)   # split 0: library's schedule (0.095 vs 0.135 ms with 3 ranges)
-                    if det:
-                        wd.accumulate = 0       # (dxT is zero: the same value) the pixel ranges of a tile as slabs, on this stream's own scratch
-                        _attach_wgrad_slabs(L_, wd, dev, st)
-                    with _timed(f"fc{li}.dgrad", "wgrad", 2.0 * N * L.Cout * L.Cin):
-                        check(L_.yolo_wgrad(ctypes.byref(wd), ptr(gT), ptr(wf), ptr(dxT), None, st), f"dgrad fc{li}")
-                    if Lc.kind == "conv":
-                        assert Lc.stride == 1, "nn.Flatten is expected after a stride-1 conv or a pool"
-                        g = self._grad_buf(ws, li - 2, N, dev)
-                        yact = y.p if Lc.lrelu else None
-                    else:
-                        g = ws["misc"].get("graw_flat")
-                        if g is None:
-                            g = Act(N, y.H, y.W, y.C, 1, dev)
-                            ws["misc"]["graw_flat"] = g
-                        yact = None
-                    check(L_.yolo_fc_dgrad_to_nhwc(ptr(dxT), N, y.C, y.H, y.W, 1, yact, self.SLOPE, g.p, st), "fc_dgrad_to_nhwc")
-                    g_act = g
-                    g_flat = None
-                    li -= 2          # nn.Flatten is done as well
-                    continue
-                if need_prev:
-                    _, wt = self._pack(li, True)
-                    d = IgemmDesc()
-                    d.N, d.Ho, d.Wo = N, 1, 1
-                    d.in_img_stride, d.in_row_stride, d.in_px_stride, d.in_off = ldg, 0, ldg, 0
-                    d.stride, d.KH, d.KW, d.tap_len, d.Cout = 1, 1, 1, ldg, L.Cin
-                    d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = L.Cin, 0, L.Cin, 0
-                    d.epilogue, d.slope, d.out_fp32, d.split_k = EPI_NONE, self.SLOPE, 1, 1
-                    gprev = torch.empty((N, L.Cin), dtype=torch.float32, device=dev)
-                    with _timed(f"fc{li}.dgrad", "igemm", 2.0 * N * L.Cout * L.Cin):
-                        _igemm(L_, d, ptr(gb), ptr(wt), None, None, ptr(gprev), st, f"dgrad fc{li}")
-                    g_flat = gprev
-                li -= 1
-            elif L.kind == "flatten":
-                raise AssertionError("nn.Flatten is handled together with the Linear layer behind it")
-            elif L.kind == "pool":
-                # g_act = gradient wrt the pooled output; produce gradient wrt the conv in front
-                lc = li - 1
-                Lc = self.layers[lc]
-                assert Lc.kind == "conv" and Lc.lrelu, "MaxPool2d is expected right after conv+LeakyReLU"
-                yfull = ws["acts"][lc]
-                if (lc == 0 and Lc.first and self.c.STEM_POOL_BWD_FUSED and Lc.Cout == 64 and Lc.Hout % 8 == 0 and Lc.Wout % 16 == 0 and g_act.halo == 1
-                        and not need_gx):      # (a gradient wrt the input image needs the stem's output gradient as a tensor)
-                    # the stem's weight-gradient kernel rebuilds this pool's (+ LeakyReLU's) backward per tile from the
-                    # activation and the pooled gradient: the 224x224x64 gradient buffer is never written or read
-                    stem_dpool = g_act
-                    li -= 1
-                    continue
-                g = self._grad_buf(ws, lc, N, dev)
-                pd = PoolDesc(N, yfull.H, yfull.W, yfull.C, 1, 1)
-                with _timed(f"pool{li}.bwd", "maxpool2_bwd"):
-                    if lc in ws.get("codes", ()):
-                        ypool = ws["acts"][li]
-                        assert (ypool.Hp, ypool.Wp, ypool.C, ypool.halo) == (g_act.Hp, g_act.Wp, g_act.C, g_act.halo)
-                        check(L_.yolo_maxpool2_bwd_codes(ctypes.byref(pd), ypool.p, ptr(ws["misc"][("codes", lc)]), g_act.p, self.SLOPE, g.p, st), "maxpool_bwd_codes")
-                    else:
-                        check(L_.yolo_maxpool2_bwd_lrelu(ctypes.byref(pd), yfull.p, g_act.p, self.SLOPE, g.p, st), "maxpool_bwd")
-                g_act = g
-                li -= 1
-            elif L.kind == "conv":
-                g = g_act  # dZ of this layer, flat-geometry buffer
-                xin = input_of(li)
-                # ---- weight + bias gradient
-                dw, db = grad_tensors(li)
-                with _on_side() as wst:
-                    o = offs[("w", li)]
-                    stem_direct = L.first and L.Cout == 64 and L.Hout % 8 == 0 and L.Wout % 16 == 0
-                    if stem_direct:
-                        part = ws["misc"].get("stem_part")
-                        if part is None:
-                            part = torch.empty((768 * 14400,), dtype=torch.float32, device=dev)
-                            ws["misc"]["stem_part"] = part
-                        with _timed(f"conv{li}.wgrad", "wgrad", 2.0 * N * L.Hout * L.Wout * L.Cout * 147):
-                            if stem_dpool is not None and 0 in ws.get("codes", ()):
-                                yp = ws["acts"][1]
-                                assert (yp.Hp, yp.Wp, yp.C, yp.halo) == (stem_dpool.Hp, stem_dpool.Wp, stem_dpool.C, stem_dpool.halo)
-                                check(L_.yolo_wgrad_stem7_codes(xin.p, yp.p, ptr(ws["misc"][("codes", 0)]), N, L.Hout, L.Wout, xin.img_stride, xin.row_stride,
-                                                                stem_dpool.p, stem_dpool.img_stride, stem_dpool.row_stride, stem_dpool.interior_off(),
-                                                                self.SLOPE if L.lrelu else 1.0, ptr(dw), ptr(db), ptr(part), part.numel(), wst), "wgrad_stem7_codes")
-                            elif stem_dpool is not None:
-                                yf = ws["acts"][0]
-                                check(L_.yolo_wgrad_stem7_pooled(xin.p, yf.p, N, L.Hout, L.Wout, xin.img_stride, xin.row_stride, yf.img_stride, yf.row_stride,
-                                                                 yf.interior_off(), stem_dpool.p, stem_dpool.img_stride, stem_dpool.row_stride,
-                                                                 stem_dpool.interior_off(), self.SLOPE if L.lrelu else 1.0, ptr(dw), ptr(db), ptr(part),
-                                                                 part.numel(), wst), "wgrad_stem7_pooled")
-                            else:
-                                check(L_.yolo_wgrad_stem7(xin.p, g.p, N, L.Hout, L.Wout, xin.img_stride, xin.row_stride, g.img_stride, g.row_stride,
-                                                          g.interior_off(), ptr(dw), ptr(db), ptr(part), part.numel(), wst), "wgrad_stem7")
-                        grads[li] = (dw, db)
-                        flush()
-                        self._layer_done(li)
-                    elif L.first:
-                        xcol = ws["misc"].get("xcol")
-                        if xcol is None:
-                            xcol = Act(N, L.Hout, L.Wout, 7 * 32, 1, dev)
-                            ws["misc"]["xcol"] = xcol
-                        check(L_.yolo_im2col_rows(xin.p, xin.img_stride, xin.row_stride, xin.px_stride, 2, 7, 32, N, L.Hout, L.Wout, 1, xcol.p, wst), "im2col_rows")
-                        dwp = scratch[o: o + L.Cout * 7 * 8 * 4]
-                        split = max(1, min(1024, g.slots // 4096))
-                        wd = WgradDesc(g.slots, g.px_stride, xcol.px_stride, L.Cout, 7 * 32, 1, 1, 0, xcol.row_stride, split, 0)
-                        if det:
-                            _attach_wgrad_slabs(L_, wd, dev, wst)
-                        with _timed(f"conv{li}.wgrad", "wgrad", 2.0 * N * L.Hout * L.Wout * L.Cout * 147):
-                            check(L_.yolo_wgrad(ctypes.byref(wd), xcol.p, g.p, ptr(dwp), ptr(db), wst), "wgrad conv0")
-                    else:
-                        dwp = scratch[o: o + L.Cout * L.K * L.K * L.Cin]
-                        # reduce over the layer's OUTPUT pixels only (not over every slot of the zero-haloed -- for stride 2
-                        # zero-stuffed -- gradient buffer, whose geometry the input buffer shares slot for slot)
-                        # (measured: worth it from 28x28 down and for stride 2; at 56x56 and above the halo is < 8 % of the slots
-                        # and the per-row coordinate arithmetic costs more than it saves)
-                        wd = self._wgrad_desc(L, g, xin, N)
-                        if det or (self.c.WGRAD_SLABS and wd.variant >= 5):
-                            _attach_wgrad_slabs(L_, wd, dev, wst)
-                        with _timed(f"conv{li}.wgrad", "wgrad", 2.0 * N * L.Hout * L.Wout * L.Cout * L.Cin * L.K * L.K):
-                            check(L_.yolo_wgrad(ctypes.byref(wd), xin.p, g.p, ptr(dwp), ptr(db), wst), f"wgrad conv{li}")
-                    if not stem_direct:
-                        grads[li] = (dw, db)
-                        pending.append((li, L, dwp, dw))
-                        if li == 0 or sum(t[2].numel() for t in pending) >= (16 << 20):
-                            flush()
-                # ---- data gradient
-                if li == 0:
-                    if side_t is not None:
-                        main_t.wait_stream(side_t)       # every weight gradient is final before anything that follows the backward pass
-                        if self.arena is not None and self.on_stream_wait is not None:
-                            self.on_stream_wait(main_t.cuda_stream, side_t.cuda_stream)
-                    gx = None
-                    if need_gx:
-                        gx = self._stem_dgrad(li, g, N, dev, st) if L.first else self._dgrad_to_input(li, g, N, dev, st)
-                    if self.debug_keep:
-                        self.last = (ws, fc_saved)
-                    else:
-                        self._release(key, ws)
-                    if self.arena is not None:
-                        if self.on_backward_done is not None:
-                            self.on_backward_done()
-                        for i in grads:          # hand the views to the optimizer without going through autograd
-                            L2 = self.layers[i]
-                            if L2.weight.grad is not grads[i][0]:
-                                L2.weight.grad = grads[i][0]
-                            if L2.bias.grad is not grads[i][1]:
-                                L2.bias.grad = grads[i][1]
-                        return gx, [None] * (2 * len(grads))
-                    return gx, [grads[i][j] for i in sorted(grads) for j in (0, 1)]
-                _, wdg = self._pack(li, True)
-                prev = self.layers[li - 1]
-                d = IgemmDesc()
-                d.N, d.Ho, d.Wo = N, L.Hin, L.Win            # gradient grid = this layer's input grid
-                d.in_img_stride, d.in_row_stride, d.in_px_stride = g.img_stride, g.row_stride, g.px_stride
-                d.in_off = g.interior_off(L.K - 1 - L.pad)
-                d.stride, d.KH, d.KW, d.tap_len, d.Cout = 1, L.K, L.K, L.Cout, L.Cin
-                d.slope, d.out_fp32, d.split_k = self.SLOPE, 0, 1
-                d.tile_hint = self.c.TILE_HINT
-                if (prev.kind == "conv" and self.c.STRIDE2_CLASSES and L.stride == 2 and L.K == 3 and L.pad == 1 and prev.stride == 1
-                        and L.Hin % 2 == 0 and L.Win % 2 == 0):
-                    # stride-2 3x3 conv: the gradient buffer g holds dy zero-stuffed to the input grid, and the plain data gradient
-                    # spends 3/4 of its MACs on those zeros.  By input-pixel parity (py, px) only the taps ky = 1 (py even) or
-                    # ky = 2, 0 (py odd; likewise kx) contribute: four small convs over the NON-ZERO slots (doubled input strides)
-                    # with 1, 2, 2 and 4 taps -- 9 taps per 2x2 input pixels instead of 36 -- each writing its parity class of the
-                    # previous layer's gradient (doubled output strides).
-                    gp = self._grad_buf(ws, li - 1, N, dev)
-                    yprev = ws["acts"][li - 1]
-                    panels = self._stride2_panels(li, wdg)
-                    with _timed(f"conv{li}.dgrad", "igemm", 2.0 * N * L.Hout * L.Wout * L.Cout * L.Cin * L.K * L.K):
-                        for (py, px), wc in panels.items():
-                            dc = IgemmDesc()
-                            dc.N, dc.Ho, dc.Wo = N, L.Hin // 2, L.Win // 2
-                            dc.in_img_stride, dc.in_row_stride, dc.in_px_stride, dc.in_off = g.img_stride, 2 * g.row_stride, 2 * g.px_stride, g.interior_off()
-                            dc.stride, dc.KH, dc.KW, dc.tap_len, dc.Cout = 1, 1 + py, 1 + px, L.Cout, L.Cin
-                            dc.slope, dc.out_fp32, dc.split_k, dc.tile_hint = self.SLOPE, 0, 1, self.c.TILE_HINT
-                            dc.out_img_stride, dc.out_row_stride, dc.out_px_stride = gp.img_stride, 2 * gp.row_stride, 2 * gp.px_stride
-                            dc.out_off = gp.interior_off() + py * gp.row_stride + px * gp.px_stride
-                            aux = None
-                            dc.epilogue = EPI_NONE
-                            if prev.lrelu:
-                                dc.epilogue = EPI_MUL_DLRELU
-                                dc.aux_img_stride, dc.aux_row_stride, dc.aux_px_stride = yprev.img_stride, 2 * yprev.row_stride, 2 * yprev.px_stride
-                                dc.aux_off = yprev.interior_off() + py * yprev.row_stride + px * yprev.px_stride
-                                aux = yprev.p
-                            igemm_call(dc, g.p, ptr(wc), None, aux, gp.p, st, f"dgrad conv{li} class {py}{px}")
-                    g_act = gp
-                elif prev.kind == "conv":
-                    gp = self._grad_buf(ws, li - 1, N, dev)
-                    d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = self._grad_out_strides(prev, gp)
-                    yprev = ws["acts"][li - 1]
-                    if prev.lrelu:
-                        d.epilogue = EPI_MUL_DLRELU
-                        d.aux_img_stride, d.aux_row_stride, d.aux_px_stride, d.aux_off = yprev.img_stride, yprev.row_stride, yprev.px_stride, yprev.interior_off()
-                        aux = yprev.p
-                    else:
-                        d.epilogue, aux = EPI_NONE, None
-                    with _timed(f"conv{li}.dgrad", "igemm", 2.0 * N * L.Hout * L.Wout * L.Cout * L.Cin * L.K * L.K):
-                        igemm_call(d, g.p, ptr(wdg), None, aux, gp.p, st, f"dgrad conv{li}")
-                    g_act = gp
-                elif prev.kind == "pool":
-                    gp = ws["misc"].get(("gpool", li))
-                    if gp is None:
-                        gp = Act(N, L.Hin, L.Win, L.Cin, 1, dev)
-                        ws["misc"][("gpool", li)] = gp
-                    d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = gp.img_stride, gp.row_stride, gp.px_stride, gp.interior_off()
-                    d.epilogue = EPI_NONE
-                    with _timed(f"conv{li}.dgrad", "igemm", 2.0 * N * L.Hout * L.Wout * L.Cout * L.Cin * L.K * L.K):
-                        igemm_call(d, g.p, ptr(wdg), None, None, gp.p, st, f"dgrad conv{li}")
-                    g_act = gp
-                else:
-                    raise AssertionError("conv after flatten/fc")
-                li -= 1
-        raise AssertionError("unreachable")
+    def _bwd_stem_wgrad(self, b, L: Layer, g: Act, xin: Act, dw, db, wst):
+        """the stem's direct weight-gradient kernel; with b.stem_dpool (the pooled gradient) it rebuilds the pool's and LeakyReLU's backward per tile,
+        from the arg-max codes or from the un-pooled activation"""
+        N, ws, L_, dp = b.N, b.ws, b.lib, b.stem_dpool
+        part = self._misc(ws, "stem_part", lambda: torch.empty((768 * 14400,), dtype=torch.float32, device=b.dev))
+        slope = self.SLOPE if L.lrelu else 1.0
+        with _timed("conv0.wgrad", "wgrad", 2.0 * N * L.Hout * L.Wout * L.Cout * 147):
+            if dp is not None and 0 in ws.get("codes", ()):
+                yp = ws["acts"][1]
+                assert (yp.Hp, yp.Wp, yp.C, yp.halo) == (dp.Hp, dp.Wp, dp.C, dp.halo)
+                check(L_.yolo_wgrad_stem7_codes(xin.p, yp.p, ptr(ws["misc"][("codes", 0)]), N, L.Hout, L.Wout, xin.img_stride, xin.row_stride,
+                                                dp.p, dp.img_stride, dp.row_stride, dp.interior_off(), slope, ptr(dw), ptr(db), ptr(part), part.numel(), wst),
+                      "wgrad_stem7_codes")
+            elif dp is not None:
+                yf = ws["acts"][0]
+                check(L_.yolo_wgrad_stem7_pooled(xin.p, yf.p, N, L.Hout, L.Wout, xin.img_stride, xin.row_stride, yf.img_stride, yf.row_stride,
+                                                 yf.interior_off(), dp.p, dp.img_stride, dp.row_stride, dp.interior_off(), slope, ptr(dw), ptr(db), ptr(part),
+                                                 part.numel(), wst), "wgrad_stem7_pooled")
+            else:
+                check(L_.yolo_wgrad_stem7(xin.p, g.p, N, L.Hout, L.Wout, xin.img_stride, xin.row_stride, g.img_stride, g.row_stride,
+                                          g.interior_off(), ptr(dw), ptr(db), ptr(part), part.numel(), wst), "wgrad_stem7")
+
+    def _bwd_conv_dgrad(self, b, li: int, g: Act):
+        """gradient wrt the output of layer li - 1 (through its LeakyReLU), or wrt the pooled map if a MaxPool2d is in front"""
+        L, prev, N, dev, ws, st = self.layers[li], self.layers[li - 1], b.N, b.dev, b.ws, b.st
+        _, wdg = self._pack(li, True)
+        flops = 2.0 * N * L.Hout * L.Wout * L.Cout * L.Cin * L.K * L.K
+        if prev.kind == "pool":
+            gp = self._misc(ws, ("gpool", li), lambda: Act(N, L.Hin, L.Win, L.Cin, 1, dev))
+            yprev = None
+        elif prev.kind == "conv":
+            gp = self._grad_buf(ws, li - 1, N, dev)
+            yprev = ws["acts"][li - 1] if prev.lrelu else None
+        else:
+            raise AssertionError("conv after flatten/fc")
+        if (prev.kind == "conv" and self.c.STRIDE2_CLASSES and L.stride == 2 and L.K == 3 and L.pad == 1 and prev.stride == 1
+                and L.Hin % 2 == 0 and L.Win % 2 == 0):
+            # stride-2 3x3 conv: the gradient buffer g holds dy zero-stuffed to the input grid, and the plain data gradient
+            # spends 3/4 of its MACs on those zeros.  By input-pixel parity (py, px) only the taps ky = 1 (py even) or
+            # ky = 2, 0 (py odd; likewise kx) contribute: four small convs over the NON-ZERO slots (doubled input strides)
+            # with 1, 2, 2 and 4 taps -- 9 taps per 2x2 input pixels instead of 36 -- each writing its parity class of the
+            # previous layer's gradient (doubled output strides).
+            with _timed(f"conv{li}.dgrad", "igemm", flops):
+                for (py, px), wc in self._stride2_panels(li, wdg).items():
+                    dc = igemm_desc(N, L.Hin // 2, L.Win // 2, 1, 1 + py, 1 + px, L.Cout, L.Cin, g, g.interior_off(), gp, 2, 2, py, px)
+                    dc.slope, dc.split_k, dc.tile_hint = self.SLOPE, 1, self.c.TILE_HINT
+                    dc.epilogue = EPI_NONE
+                    if yprev is not None:
+                        dc.epilogue = EPI_MUL_DLRELU
+                        desc_aux(dc, yprev, 2, py, px)
+                    igemm_call(dc, g.p, ptr(wc), None, yprev.p if yprev is not None else None, gp.p, st, f"dgrad conv{li} class {py}{px}")
+        else:
+            # the previous layer's gradient buffer has ITS input geometry: zero-stuffed if that layer has stride 2
+            d = self._dgrad_desc(L, g, N, gp, 2 if (prev.kind == "conv" and prev.stride != 1 and not prev.first) else 1)
+            d.tile_hint = self.c.TILE_HINT
+            d.epilogue = EPI_NONE
+            if yprev is not None:
+                d.epilogue = EPI_MUL_DLRELU
+                desc_aux(d, yprev)
+            with _timed(f"conv{li}.dgrad", "igemm", flops):
+                igemm_call(d, g.p, ptr(wdg), None, yprev.p if yprev is not None else None, gp.p, st, f"dgrad conv{li}")
+        b.g_act = gp
+
+    def _finish_backward(self, b):
+        """join the streams, the gradient wrt the plan's input if asked for, the workspace back to its pool, gradients to the arena's owner or to autograd"""
+        L = self.layers[0]
+        assert L.kind == "conv", "plans start with a conv layer"
+        if b.side_t is not None:
+            b.main_t.wait_stream(b.side_t)       # every weight gradient is final before anything that follows the backward pass
+            if self.arena is not None and self.on_stream_wait is not None:
+                self.on_stream_wait(b.main_t.cuda_stream, b.side_t.cuda_stream)
+        gx = None
+        if b.need_gx:
+            gx = (self._stem_dgrad if L.first else self._dgrad_to_input)(0, b.g_act, b.N, b.dev, b.st)
+        if self.debug_keep:
+            self.last = (b.ws, b.fc_saved)
+        else:
+            self._release(b.key, b.ws)
+        grads = b.grads
+        if self.arena is None:
+            return gx, [grads[i][j] for i in sorted(grads) for j in (0, 1)]
+        if self.on_backward_done is not None:
+            self.on_backward_done()
+        for i in grads:          # hand the views to the optimizer without going through autograd
+            L2 = self.layers[i]
+            if L2.weight.grad is not grads[i][0]:
+                L2.weight.grad = grads[i][0]
+            if L2.bias.grad is not grads[i][1]:
+                L2.bias.grad = grads[i][1]
+        return gx, [None] * (2 * len(grads))
 
     def _apply_dlrelu_into(self, graw: Act, y: Act, L: Layer, g: Act, st):
         """g(interior, possibly zero-stuffed) = graw * lrelu'(y) -- used only at plan ends (rare path)."""
@@ -1069,11 +969,8 @@ class Plan:
                 kxs = [px + 5 - 2 * t for t in range(3 + px)]
                 panel = torch.zeros((8, len(kys), len(kxs), L.Cout), dtype=torch.bfloat16, device=dev)
                 panel[:3] = w[:, :, kys][:, :, :, kxs].permute(1, 2, 3, 0).to(torch.bfloat16)      # [c][ty][tx][co]
-                d = IgemmDesc()
-                d.N, d.Ho, d.Wo = N, L.Hout, L.Wout
-                d.in_img_stride, d.in_row_stride, d.in_px_stride, d.in_off = g.img_stride, g.row_stride, g.px_stride, g.interior_off(1)
-                d.stride, d.KH, d.KW, d.tap_len, d.Cout = 1, len(kys), len(kxs), L.Cout, 8
-                d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = H * W * 8, 2 * W * 8, 16, (py * W + px) * 8
+                d = igemm_desc(N, L.Hout, L.Wout, 1, len(kys), len(kxs), L.Cout, 8, g, g.interior_off(1))
+                d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = H * W * 8, 2 * W * 8, 16, (py * W + px) * 8     # (a plain tensor, not an Act)
                 d.epilogue, d.slope, d.out_fp32, d.split_k, d.tile_hint = EPI_NONE, self.SLOPE, 1, 1, 4      # 64 x 128 tiles: 8 "channels"
                 _igemm(L_, d, g.p, ptr(panel), None, None, ptr(buf), st, f"stem dgrad class {py}{px}")
         return buf[..., :3].permute(0, 3, 1, 2).contiguous()
@@ -1083,15 +980,81 @@ class Plan:
         L = self.layers[li]
         _, wdg = self._pack(li, True)
         gi = Act(N, L.Hin, L.Win, L.Cin, 1, dev)
-        d = IgemmDesc()
-        d.N, d.Ho, d.Wo = N, L.Hin, L.Win
-        d.in_img_stride, d.in_row_stride, d.in_px_stride = g.img_stride, g.row_stride, g.px_stride
-        d.in_off = g.interior_off(L.K - 1 - L.pad)
-        d.stride, d.KH, d.KW, d.tap_len, d.Cout = 1, L.K, L.K, L.Cout, L.Cin
-        d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = gi.img_stride, gi.row_stride, gi.px_stride, gi.interior_off()
-        d.epilogue, d.slope, d.out_fp32, d.split_k = EPI_NONE, self.SLOPE, 0, 1
+        d = self._dgrad_desc(L, g, N, gi)
+        d.epilogue = EPI_NONE
         _igemm(RT.lib(), d, g.p, ptr(wdg), None, None, gi.p, st, "dgrad input")
         gx = torch.empty((N, L.Cin, L.Hin, L.Win), dtype=torch.float32, device=dev)
         check(RT.lib().yolo_nhwc_bf16_to_nchw_f32(gi.p, N, L.Cin, L.Hin, L.Win, 1, ptr(gx), st), "gx nhwc->nchw")
         return gx
 
+
+class _Pass:
+    """what the steps of one forward pass share: the workspace, the batch, the stream, and the activation flowing from layer to layer (``cur``)"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class _Backward:
+    """State of one backward pass: the workspace and batch of its forward, both streams, the scratch areas of the weight gradients, the gradients
+    made so far, and the gradient flowing from layer to layer -- ``g_flat``, fp32 (N, K) rows in front of an fc layer, or ``g_act``, an Act wrt a
+    conv / pool output (already through LeakyReLU')."""
+
+    def __init__(self, plan: Plan, saved, need_gx: bool):
+        self.plan, self.need_gx = plan, need_gx
+        self.lib, self.st = RT.lib(), RT.stream()
+        self.key, self.ws, self.fc_saved, self.N, self.dev = saved
+        dev = self.dev
+        plan._apply_geom(self.ws)
+        if plan.arena is not None:
+            plan.arena[plan._arena_w_end:].zero_()      # bias gradients are accumulated with atomics
+        # two zero-filled fp32 scratch areas for the whole pass: the packed conv weight gradients (targets of yolo_wgrad's atomics; a buffer
+        # of the workspace, cleared ON THE SIDE STREAM, where its first user runs: 80 MB of fill off the data-gradient chain) and,
+        # without an arena, the bias gradients (fresh every pass: they are handed to autograd) -- two fills instead of ~50
+        self.offs, tot, btot = {}, 0, 0
+        for i, L in enumerate(plan.layers):
+            if L.kind == "conv":
+                self.offs[("w", i)] = tot
+                tot += _round_up(L.Cout * 7 * 8 * 4 if L.first else L.Cout * L.K * L.K * L.Cin, 64)
+            if L.kind in ("conv", "fc") and plan.arena is None:
+                self.offs[("b", i)] = btot
+                btot += _round_up(L.Cout, 64)
+        self.scratch = self.ws["misc"].get("wgrad_scratch")
+        if self.scratch is None or self.scratch.numel() < tot:
+            self.scratch = self.ws["misc"]["wgrad_scratch"] = torch.empty(max(tot, 1), dtype=torch.float32, device=dev)
+        self.bscratch = torch.zeros(max(btot, 1), dtype=torch.float32, device=dev)
+        self.main_t = RT.STREAMS.current(dev)
+        self.side_t = plan._side_stream(dev) if plan.c.WGRAD_STREAM else None
+        self.det = bool(plan.c.DETERMINISTIC)     # every yolo_wgrad launch with slabs (scratch per stream), no norm hint (EngineConfig.DETERMINISTIC)
+        self.grads: dict[int, tuple] = {}
+        self.pending: list[tuple] = []     # conv gradients waiting for their packed -> OIHW conversion
+        self.fc_keep: list = []
+        self.stem_dpool = None             # pooled gradient handed straight to the stem's weight-gradient kernel (pool backward fused there)
+        self.g_flat = self.g_act = None
+
+    def on_side(self, side: bool = True):
+        """``with b.on_side() as st:`` -- the second stream, behind everything queued on the main one (the main stream itself without one / if not side)"""
+        return _on_side_stream(self.main_t, self.side_t if side else None, self.plan.on_stream_wait if self.plan.arena is not None else None)
+
+    def grad_tensors(self, i: int):
+        """(dw, db) of layer i: the arena's views, or a fresh weight gradient and a slice of the zeroed bias scratch"""
+        if self.plan.arena is not None:
+            dw, db, _, _ = self.plan.arena_views[i]
+            return dw, db
+        L = self.plan.layers[i]
+        o = self.offs[("b", i)]
+        return torch.empty_like(L.weight, dtype=torch.float32), self.bscratch[o: o + L.Cout]
+
+    def flush(self):
+        """packed -> OIHW conversion of the finished conv gradients, several layers per launch (yolo_unpack_conv_wgrads_multi) on the current
+        stream; the gradients are final (and announced) here"""
+        plan, L_ = self.plan, self.lib
+        items = [ConvUnpackItem(dwp.data_ptr(), dw.data_ptr(), L.Cout, L.Cin, L.K, L.K) for (i, L, dwp, dw) in self.pending if plan._multi_ok(L)]
+        if items:
+            check(L_.yolo_unpack_conv_wgrads_multi((ConvUnpackItem * len(items))(*items), len(items), RT.stream()), "unpack_conv_wgrads_multi")
+        for (i, L, dwp, dw) in self.pending:
+            if not plan._multi_ok(L):
+                shape = (3, 7, 7, 4, 8) if L.first else (L.Cin, L.K, L.K, L.Cin, L.K)          # (the stem's panel: rows of 8 taps x 4 channels)
+                check(L_.yolo_unpack_conv_wgrad(ptr(dwp), L.Cout, *shape, ptr(dw), 0, RT.stream()), "unpack")
+            plan._layer_done(i)
+        self.pending.clear()

@@ -13,7 +13,7 @@ from ._hip import (EPI_BIAS, EPI_BIAS_LRELU, EPI_NONE, ConvPackItem, ConvUnpackI
 from .config import CONFIG as CFG
 from .executor import Plan
 from .plans import igemm_call
-from .runtime import RT, Act, _igemm, _on_side_stream, _round_up, _timed
+from .runtime import RT, Act, _igemm, _on_side_stream, _round_up, _timed, desc_aux, igemm_desc, stem_tiles_ok
 
 # ====================================================================================================
 # ResNet-50 trunk, inference only (BatchNorm folded into the conv that precedes it)
@@ -127,16 +127,9 @@ class ResNetPlan:
 
     def _conv_bn_train(self, tag, a_in: Act, packed, N, relu: bool, residual: Act | None, dev, st):
         wf, _, conv, bn = packed
-        k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        Ho, Wo = (a_in.H + 2 * p - k) // s + 1, (a_in.W + 2 * p - k) // s + 1
+        k, s, p, Ho, Wo = self._geom(a_in, conv)
         a_out = self._act(tag, N, Ho, Wo, conv.out_channels, 1, dev)
-        d = IgemmDesc()
-        d.N, d.Ho, d.Wo = N, Ho, Wo
-        d.in_img_stride, d.in_row_stride, d.in_px_stride = a_in.img_stride, a_in.row_stride, a_in.px_stride
-        d.in_off = a_in.interior_off(p)
-        d.stride, d.KH, d.KW, d.tap_len, d.Cout = s, k, k, conv.in_channels, conv.out_channels
-        d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = a_out.img_stride, a_out.row_stride, a_out.px_stride, a_out.interior_off()
-        d.epilogue, d.slope = EPI_NONE, 1.0
+        d = self._desc(a_in, p, s, k, a_out, EPI_NONE, 1.0)
         d.bn_stats = self._scratch(dev)[0].data_ptr() if CFG.BN_STATS_IN_CONV else None      # the conv's epilogue accumulates BatchNorm's sums
         with _timed(str(tag), "igemm", 2.0 * N * Ho * Wo * conv.out_channels * conv.in_channels * k * k):
             igemm_call(d, a_in.p, ptr(wf), None, None, a_out.p, st, f"igemm {tag}")
@@ -150,37 +143,20 @@ class ResNetPlan:
         _hip.require_cuda(x)
         st = RT.stream()
         pk = self._pack_raw()
-        N, _, H, W = x.shape
-        dev = x.device
-        x = x.detach()
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.float().contiguous()
-        a = self._act("in", N, H, W, 4, 3, dev)
-        check(RT.lib().yolo_nchw_f32_to_nhwc_bf16(ptr(x), N, 3, H, W, a.p, 4, 3, 3, st), "nchw->nhwc4")
+        N, dev = x.shape[0], x.device
+        a, Ho, Wo = self._stem_input(x, st)
         wf, _, conv, bn = pk["stem"]
-        Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
         s1 = self._act("stem", N, Ho, Wo, 64, 1, dev)
-        d = IgemmDesc()
-        d.N, d.Ho, d.Wo = N, Ho, Wo
-        d.in_img_stride, d.in_row_stride, d.in_px_stride, d.in_off = a.img_stride, a.row_stride, a.px_stride, 0
-        d.stride, d.KH, d.KW, d.tap_len, d.Cout = 2, 7, 1, 32, 64
-        d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = s1.img_stride, s1.row_stride, s1.px_stride, s1.interior_off()
-        d.epilogue, d.slope = EPI_NONE, 1.0
-        _igemm(RT.lib(), d, a.p, ptr(wf), None, None, s1.p, st, "igemm stem")
+        _igemm(RT.lib(), self._stem_desc(a, s1, EPI_NONE, 1.0), a.p, ptr(wf), None, None, s1.p, st, "igemm stem")
         self._bn_train(s1, bn, True, None, dev, st)
-        Hq, Wq = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
-        cur = self._act("pool", N, Hq, Wq, 64, 1, dev)
-        pd = PoolDesc(N, Ho, Wo, 64, 1, 1)
-        check(RT.lib().yolo_maxpool3s2_fwd(ctypes.byref(pd), s1.p, cur.p, st), "maxpool3s2")
+        cur = self._stem_pool(s1, dev, st)
         for li in range(4, 8):
             for bi, blk in enumerate(self.trunk[li]):
                 idn = cur if blk.downsample is None else self._conv_bn_train((li, bi, "d"), cur, pk[(li, bi, "d")], N, False, None, dev, st)
                 t = self._conv_bn_train((li, bi, 1), cur, pk[(li, bi, 1)], N, True, None, dev, st)
                 t = self._conv_bn_train((li, bi, 2), t, pk[(li, bi, 2)], N, True, None, dev, st)
                 cur = self._conv_bn_train((li, bi, 3), t, pk[(li, bi, 3)], N, True, idn, dev, st)
-        out = torch.empty((N, cur.C, cur.H, cur.W), dtype=torch.float32, device=dev)
-        check(RT.lib().yolo_nhwc_bf16_to_nchw_f32(cur.p, N, cur.C, cur.H, cur.W, cur.halo, ptr(out), st), "nhwc->nchw")
-        return out
+        return self._to_nchw(cur, dev, st)
 
     # ------------------------------------------------------------------ trainable trunk (forward keeps z, backward)
     def _pack_train(self):
@@ -230,17 +206,10 @@ class ResNetPlan:
     def _unit_fwd(self, tag, a_in: Act, packed, N, relu: bool, residual: Act | None, stats: torch.Tensor, dev, st, frozen: bool = False):
         """conv -> z (kept) -> BatchNorm(batch statistics; frozen: running statistics) [+ residual] [ReLU] -> y; returns the record the backward needs."""
         wf, wd, conv, bn = packed
-        k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        Ho, Wo = (a_in.H + 2 * p - k) // s + 1, (a_in.W + 2 * p - k) // s + 1
+        k, s, p, Ho, Wo = self._geom(a_in, conv)
         z = self._act((tag, "z"), N, Ho, Wo, conv.out_channels, 1, dev)
         y = self._act((tag, "y"), N, Ho, Wo, conv.out_channels, 1, dev)
-        d = IgemmDesc()
-        d.N, d.Ho, d.Wo = N, Ho, Wo
-        d.in_img_stride, d.in_row_stride, d.in_px_stride = a_in.img_stride, a_in.row_stride, a_in.px_stride
-        d.in_off = a_in.interior_off(p)
-        d.stride, d.KH, d.KW, d.tap_len, d.Cout = s, k, k, conv.in_channels, conv.out_channels
-        d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = z.img_stride, z.row_stride, z.px_stride, z.interior_off()
-        d.epilogue, d.slope = EPI_NONE, 1.0
+        d = self._desc(a_in, p, s, k, z, EPI_NONE, 1.0)
         in_conv = CFG.BN_STATS_IN_CONV and not frozen
         d.bn_stats = self._scratch(dev)[0].data_ptr() if in_conv else None      # the conv's epilogue accumulates BatchNorm's sums
         with _timed(str(tag), "igemm", 2.0 * N * Ho * Wo * conv.out_channels * conv.in_channels * k * k):
@@ -259,12 +228,8 @@ class ResNetPlan:
         _hip.require_cuda(x)
         st = RT.stream()
         pk = self._pack_train()
-        N, _, H, W = x.shape
-        dev = x.device
-        x = x.detach()
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.float().contiguous()
-        Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+        N, dev = x.shape[0], x.device
+        a, Ho, Wo = self._stem_input(x, st)
         nstat = 4 * (64 + sum(u.num_features for u in self.trunk.modules() if isinstance(u, nn.BatchNorm2d)))
         if getattr(self, "_stats", None) is None or self._stats.numel() < nstat or self._stats.device != dev:
             self._stats = torch.empty(nstat, dtype=torch.float32, device=dev)
@@ -275,24 +240,13 @@ class ResNetPlan:
             cursor[0] += 4 * C
             return t
 
-        a = self._act("in", N, H, W, 4, 3, dev)
-        check(RT.lib().yolo_nchw_f32_to_nhwc_bf16(ptr(x), N, 3, H, W, a.p, 4, 3, 3, st), "nchw->nhwc4")
         wf, _, conv, bn = pk["stem"]
         z0 = self._act(("stem", "z"), N, Ho, Wo, 64, 1, dev)
         y0 = self._act(("stem", "y"), N, Ho, Wo, 64, 1, dev)
-        d = IgemmDesc()
-        d.N, d.Ho, d.Wo = N, Ho, Wo
-        d.in_img_stride, d.in_row_stride, d.in_px_stride, d.in_off = a.img_stride, a.row_stride, a.px_stride, 0
-        d.stride, d.KH, d.KW, d.tap_len, d.Cout = 2, 7, 1, 32, 64
-        d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = z0.img_stride, z0.row_stride, z0.px_stride, z0.interior_off()
-        d.epilogue, d.slope = EPI_NONE, 1.0
-        _igemm(RT.lib(), d, a.p, ptr(wf), None, None, z0.p, st, "igemm stem")
+        _igemm(RT.lib(), self._stem_desc(a, z0, EPI_NONE, 1.0), a.p, ptr(wf), None, None, z0.p, st, "igemm stem")
         stem = {"tag": "stem", "conv": conv, "bn": bn, "x": a, "z": z0, "y": y0, "relu": True, "res": False, "stats": stat(64)}
         self._bn_train(z0, bn, True, None, dev, st, out=y0, save=stem["stats"], frozen=frozen)
-        Hq, Wq = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
-        cur = self._act("pool", N, Hq, Wq, 64, 1, dev)
-        pd = PoolDesc(N, Ho, Wo, 64, 1, 1)
-        check(RT.lib().yolo_maxpool3s2_fwd(ctypes.byref(pd), y0.p, cur.p, st), "maxpool3s2")
+        cur = self._stem_pool(y0, dev, st)
         blocks = []
         for li in range(4, 8):
             for bi, blk in enumerate(self.trunk[li]):
@@ -306,8 +260,7 @@ class ResNetPlan:
                 u3 = self._unit_fwd((li, bi, 3), u2["y"], pk[(li, bi, 3)], N, True, idn, stat(blk.bn3.num_features), dev, st, frozen)
                 blocks.append((li, bi, u1, u2, u3, ud))
                 cur = u3["y"]
-        out = torch.empty((N, cur.C, cur.H, cur.W), dtype=torch.float32, device=dev)
-        check(RT.lib().yolo_nhwc_bf16_to_nchw_f32(cur.p, N, cur.C, cur.H, cur.W, cur.halo, ptr(out), st), "nhwc->nchw")
+        out = self._to_nchw(cur, dev, st)
         self._train_gen = getattr(self, "_train_gen", 0) + 1
         return out, {"N": N, "dev": dev, "stem": stem, "blocks": blocks, "out": cur, "gen": self._train_gen, "frozen": frozen}
 
@@ -388,18 +341,12 @@ class ResNetPlan:
         def dgrad(u, dz: Act, add: Act | None) -> Act:
             conv, xin, k, p = u["conv"], u["x"], u["k"], u["p"]
             g = self._act((u["tag"], "gx"), N, xin.H, xin.W, conv.in_channels, 1, dev)
-            d = IgemmDesc()
-            d.N, d.Ho, d.Wo = N, xin.H, xin.W
-            d.in_img_stride, d.in_row_stride, d.in_px_stride = dz.img_stride, dz.row_stride, dz.px_stride
-            d.in_off = dz.interior_off(k - 1 - p)
-            d.stride, d.KH, d.KW, d.tap_len, d.Cout = 1, k, k, conv.out_channels, conv.in_channels
-            d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = g.img_stride, g.row_stride, g.px_stride, g.interior_off()
-            d.slope, d.out_fp32, d.split_k = 1.0, 0, 1
+            d = self._desc(dz, k - 1 - p, 1, k, g, EPI_NONE, 1.0)         # over the conv's input grid, with the flipped panel
+            d.split_k = 1
             aux, bias = None, None
-            d.epilogue = EPI_NONE
             if add is not None:
                 d.epilogue = _hip.EPI_BIAS_ADD_LRELU          # slope 1: out = conv + 0 + aux
-                d.aux_img_stride, d.aux_row_stride, d.aux_px_stride, d.aux_off = add.img_stride, add.row_stride, add.px_stride, add.interior_off()
+                desc_aux(d, add)
                 aux, bias = add.p, ptr(self._zero_bias)
             with _timed(f"{u['tag']}.dgrad", "igemm", 2.0 * N * xin.H * xin.W * conv.out_channels * conv.in_channels * k * k):
                 igemm_call(d, dz.p, ptr(u["wd"]), bias, aux, g.p, st, f"dgrad {u['tag']}")
@@ -447,7 +394,7 @@ class ResNetPlan:
         if part is None or part.device != dev:
             part = self._stem_part = torch.empty((768 * 14400,), dtype=torch.float32, device=dev)
             self._stem_db = torch.empty(64, dtype=torch.float32, device=dev)
-        if y0.H % 8 == 0 and y0.W % 16 == 0:
+        if stem_tiles_ok(64, y0.H, y0.W):
             check(L_.yolo_wgrad_stem7(xin.p, dz0.p, N, y0.H, y0.W, xin.img_stride, xin.row_stride, dz0.img_stride, dz0.row_stride, dz0.interior_off(),
                                       ptr(dw), ptr(self._stem_db), ptr(part), part.numel(), st), "wgrad_stem7")
         else:
@@ -472,25 +419,60 @@ class ResNetPlan:
             self._bufs[k] = a
         return a
 
+    # ------------------------------------------------------------------ what the three forwards and the backward share
+    @staticmethod
+    def _geom(a_in: Act, conv: nn.Conv2d):
+        """(k, stride, pad, Ho, Wo) of conv over a_in"""
+        k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        return k, s, p, (a_in.H + 2 * p - k) // s + 1, (a_in.W + 2 * p - k) // s + 1
+
+    @staticmethod
+    def _desc(a_in: Act, shift: int, stride: int, k: int, a_out: Act, epilogue: int, slope: float) -> IgemmDesc:
+        """a k x k conv that reads a_in from `shift` pixels up / left of its interior and fills a_out's interior, channels as the buffers have them"""
+        d = igemm_desc(a_out.N, a_out.H, a_out.W, stride, k, k, a_in.C, a_out.C, a_in, a_in.interior_off(shift), a_out)
+        d.epilogue, d.slope = epilogue, slope
+        return d
+
+    def _stem_input(self, x: torch.Tensor, st):
+        """the batch as the stem reads it -> (NHWC4 bf16 copy with a halo of 3, output height, output width of the 7x7/s2/p3 conv)"""
+        N, _, H, W = x.shape
+        x = x.detach()
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.float().contiguous()
+        a = self._act("in", N, H, W, 4, 3, x.device)
+        check(RT.lib().yolo_nchw_f32_to_nhwc_bf16(ptr(x), N, 3, H, W, a.p, 4, 3, 3, st), "nchw->nhwc4")
+        return a, (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+
+    @staticmethod
+    def _stem_desc(a: Act, out: Act, epilogue: int, slope: float) -> IgemmDesc:
+        """the stem as a row-segment implicit GEMM: 7 taps of 8 pixels x 4 channels per output pixel"""
+        d = igemm_desc(a.N, out.H, out.W, 2, 7, 1, 32, 64, a, 0, out)
+        d.epilogue, d.slope = epilogue, slope
+        return d
+
+    def _stem_pool(self, y: Act, dev, st) -> Act:
+        """MaxPool2d(3,2,1) behind the stem"""
+        cur = self._act("pool", y.N, (y.H - 1) // 2 + 1, (y.W - 1) // 2 + 1, 64, 1, dev)
+        pd = PoolDesc(y.N, y.H, y.W, 64, 1, 1)
+        check(RT.lib().yolo_maxpool3s2_fwd(ctypes.byref(pd), y.p, cur.p, st), "maxpool3s2")
+        return cur
+
+    @staticmethod
+    def _to_nchw(cur: Act, dev, st) -> torch.Tensor:
+        out = torch.empty((cur.N, cur.C, cur.H, cur.W), dtype=torch.float32, device=dev)
+        check(RT.lib().yolo_nhwc_bf16_to_nchw_f32(cur.p, cur.N, cur.C, cur.H, cur.W, cur.halo, ptr(out), st), "nhwc->nchw")
+        return out
+
     def _conv(self, tag, a_in: Act, packed, N, relu: bool, residual: Act | None, dev, st):
         wf, b, conv = packed
-        k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        Ho, Wo = (a_in.H + 2 * p - k) // s + 1, (a_in.W + 2 * p - k) // s + 1
+        k, s, p, Ho, Wo = self._geom(a_in, conv)
         a_out = self._act(tag, N, Ho, Wo, conv.out_channels, 1, dev)
-        d = IgemmDesc()
-        d.N, d.Ho, d.Wo = N, Ho, Wo
-        d.in_img_stride, d.in_row_stride, d.in_px_stride = a_in.img_stride, a_in.row_stride, a_in.px_stride
-        d.in_off = a_in.interior_off(p)
-        d.stride, d.KH, d.KW, d.tap_len, d.Cout = s, k, k, conv.in_channels, conv.out_channels
-        d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = a_out.img_stride, a_out.row_stride, a_out.px_stride, a_out.interior_off()
-        d.slope = 0.0 if relu else 1.0
+        d = self._desc(a_in, p, s, k, a_out, EPI_BIAS_LRELU if relu else EPI_BIAS, 0.0 if relu else 1.0)
         aux = None
         if residual is not None:
             d.epilogue = _hip.EPI_BIAS_ADD_LRELU
-            d.aux_img_stride, d.aux_row_stride, d.aux_px_stride, d.aux_off = residual.img_stride, residual.row_stride, residual.px_stride, residual.interior_off()
+            desc_aux(d, residual)
             aux = residual.p
-        else:
-            d.epilogue = EPI_BIAS_LRELU if relu else EPI_BIAS
         with _timed(str(tag), "igemm", 2.0 * N * Ho * Wo * conv.out_channels * conv.in_channels * k * k):
             igemm_call(d, a_in.p, ptr(wf), ptr(b), aux, a_out.p, st, f"igemm {tag}")
         return a_out
@@ -501,40 +483,23 @@ class ResNetPlan:
         _hip.require_cuda(x)
         st = RT.stream()
         pk = self._pack_all()
-        N, _, H, W = x.shape
-        dev = x.device
-        x = x.detach()
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.float().contiguous()
-        a = self._act("in", N, H, W, 4, 3, dev)
-        check(RT.lib().yolo_nchw_f32_to_nhwc_bf16(ptr(x), N, 3, H, W, a.p, 4, 3, 3, st), "nchw->nhwc4")
-        # stem: 7x7/s2 (+BN+ReLU) as the row-segment implicit GEMM, then MaxPool2d(3,2,1)
+        N, dev = x.shape[0], x.device
+        a, Ho, Wo = self._stem_input(x, st)
+        # stem: 7x7/s2 (+BN+ReLU) through its dedicated kernel or as the row-segment implicit GEMM, then MaxPool2d(3,2,1)
         wf, b, conv = pk["stem"]
-        Ho, Wo = (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
         s1 = self._act("stem", N, Ho, Wo, 64, 1, dev)
-        d = IgemmDesc()
-        d.N, d.Ho, d.Wo = N, Ho, Wo
-        d.in_img_stride, d.in_row_stride, d.in_px_stride, d.in_off = a.img_stride, a.row_stride, a.px_stride, 0
-        d.stride, d.KH, d.KW, d.tap_len, d.Cout = 2, 7, 1, 32, 64
-        d.out_img_stride, d.out_row_stride, d.out_px_stride, d.out_off = s1.img_stride, s1.row_stride, s1.px_stride, s1.interior_off()
-        d.epilogue, d.slope = EPI_BIAS_LRELU, 0.0
-        if CFG.STEM_KERNEL and Ho % 8 == 0 and Wo % 16 == 0:
+        if CFG.STEM_KERNEL and stem_tiles_ok(64, Ho, Wo):
             with _timed("stem", "stem", 2.0 * N * Ho * Wo * 64 * 147):
                 check(RT.lib().yolo_conv_stem7_fwd(a.p, ptr(wf), ptr(b), N, Ho, Wo, a.img_stride, a.row_stride, 0.0, 0, s1.p, s1.img_stride, s1.row_stride,
                                                 s1.interior_off(), None, 0, 0, 0, st), "conv_stem7_fwd")
         else:
             with _timed("stem", "igemm", 2.0 * N * Ho * Wo * 64 * 147):
-                _igemm(RT.lib(), d, a.p, ptr(wf), ptr(b), None, s1.p, st, "igemm stem")
-        Hq, Wq = (Ho - 1) // 2 + 1, (Wo - 1) // 2 + 1
-        cur = self._act("pool", N, Hq, Wq, 64, 1, dev)
-        pd = PoolDesc(N, Ho, Wo, 64, 1, 1)
-        check(RT.lib().yolo_maxpool3s2_fwd(ctypes.byref(pd), s1.p, cur.p, st), "maxpool3s2")
+                _igemm(RT.lib(), self._stem_desc(a, s1, EPI_BIAS_LRELU, 0.0), a.p, ptr(wf), ptr(b), None, s1.p, st, "igemm stem")
+        cur = self._stem_pool(s1, dev, st)
         for li in range(4, 8):
             for bi, blk in enumerate(self.trunk[li]):
                 idn = cur if blk.downsample is None else self._conv((li, bi, "d"), cur, pk[(li, bi, "d")], N, False, None, dev, st)
                 t = self._conv((li, bi, 1), cur, pk[(li, bi, 1)], N, True, None, dev, st)
                 t = self._conv((li, bi, 2), t, pk[(li, bi, 2)], N, True, None, dev, st)
                 cur = self._conv((li, bi, 3), t, pk[(li, bi, 3)], N, True, idn, dev, st)
-        out = torch.empty((N, cur.C, cur.H, cur.W), dtype=torch.float32, device=dev)
-        check(RT.lib().yolo_nhwc_bf16_to_nchw_f32(cur.p, N, cur.C, cur.H, cur.W, cur.halo, ptr(out), st), "nhwc->nchw")
-        return out
+        return self._to_nchw(cur, dev, st)

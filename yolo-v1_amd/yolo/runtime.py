@@ -9,7 +9,7 @@ import ctypes
 import torch
 
 from . import _hip
-from ._hip import WgradDesc, check
+from ._hip import IgemmDesc, WgradDesc, check
 from .config import CONFIG as CFG
 
 
@@ -20,6 +20,36 @@ def _round_up(a: int, b: int) -> int:
 def _igemm(L_, d, inp, w, bias, aux, out, st, what):
     CFG.IGEMM_LAUNCHES += 1
     check(L_.yolo_igemm(ctypes.byref(d), inp, w, bias, aux, out, st), what)
+
+
+# ---- yolo_igemm descriptors: the one place that knows how an ``Act`` (defined below) maps onto the in / out / aux sides of an ``IgemmDesc``.  Each builder
+# sets exactly the fields named here; everything else (epilogue, slope, tile hints, split_k ..) stays zero until the call site sets it.
+def igemm_desc(N, Ho, Wo, stride, KH, KW, tap_len, Cout, a_in: "Act", in_off: int, a_out: "Act | None" = None, in_mul: int = 1, out_mul: int = 1,
+               py: int = 0, px: int = 0) -> IgemmDesc:
+    """Problem geometry (an N x Ho x Wo output grid, KH x KW taps of tap_len channels at the given stride, Cout output channels), input side (a_in's
+    strides, the first tap at element in_off) and, with a_out, output side (its interior).  in_mul = 2 reads every other slot (the non-zero slots of a
+    zero-stuffed gradient); out_mul = 2 writes every other slot, from pixel (py, px) on: a parity class, or zero-stuffing.  One constructor call: these
+    are the struct's leading fields, in its order (a forward at batch 1 is bound by this host code)."""
+    if a_out is None:
+        return IgemmDesc(N, Ho, Wo, a_in.img_stride, in_mul * a_in.row_stride, in_mul * a_in.px_stride, in_off, stride, KH, KW, tap_len, Cout)
+    return IgemmDesc(N, Ho, Wo, a_in.img_stride, in_mul * a_in.row_stride, in_mul * a_in.px_stride, in_off, stride, KH, KW, tap_len, Cout,
+                     a_out.img_stride, out_mul * a_out.row_stride, out_mul * a_out.px_stride, a_out.interior_off() + py * a_out.row_stride + px * a_out.px_stride)
+
+
+def rows_desc(N, ld_in, K, Cout) -> IgemmDesc:
+    """a Linear layer: N rows of K inputs (leading dimension ld_in) -> N dense rows of Cout outputs, as a 1 x 1 conv over a 1 x 1 grid"""
+    return IgemmDesc(N, 1, 1, ld_in, 0, ld_in, 0, 1, 1, 1, K, Cout, Cout, 0, Cout, 0)
+
+
+def desc_aux(d: IgemmDesc, a: "Act", mul: int = 1, py: int = 0, px: int = 0) -> None:
+    """aux side (second input or second output of an epilogue), addressed like the output side of igemm_desc"""
+    d.aux_img_stride, d.aux_row_stride, d.aux_px_stride = a.img_stride, mul * a.row_stride, mul * a.px_stride
+    d.aux_off = a.interior_off() + py * a.row_stride + px * a.px_stride
+
+
+def stem_tiles_ok(Cout: int, Hout: int, Wout: int) -> bool:
+    """the dedicated 7x7/s2 stem kernels (forward, weight gradient, fused pool backward) cover this output map: 64 channels in 8 x 16-pixel tiles"""
+    return Cout == 64 and Hout % 8 == 0 and Wout % 16 == 0
 
 
 class _Streams:
