@@ -509,6 +509,30 @@ int yolo_sgd_step_multi_bg(const yolo_sgd_tensor *t, int count, float lr, float 
                            int nesterov, int first_step, const double *norm_sq, float max_norm, const float *skip_flag,
                            int workgroups, yolo_stream_t stream);
 
+/* Exponential moving average of the weights, the copy a detector validates and ships: replaces
+ * torch.optim.swa_utils.get_ema_multi_avg_fn / torch._foreach_lerp_(ema, params, 1 - decay) (the reference keeps no EMA; its
+ * train step is src/yolo/training/trainer.py:79-95, and the average follows optimizer.step()).  Per element, in fp32:
+ *     e = fmaf(w, p - e, e)             w = (float)(1.0 - decay), formed by the host in double
+ * -- one rounding for the difference, one for the fused multiply-add (torch.lerp's form for weights below 0.5); all three forms
+ * compute the same bits.  p is only read.  *skip_flag != 0 (device float, NULL: none) updates nothing: a step the optimizer
+ * skipped is no EMA step.
+ * YOLO_E_ARG: a null pointer, n < 0, w outside [0, 1] or NaN, workgroups outside 1 .. 256, more than YOLO_MT_MAX tensors in the
+ * background form.  YOLO_E_UNSUPPORTED: ema or p not 16-B aligned, ema overlapping p.  Either way nothing is launched. */
+typedef struct yolo_ema_tensor {
+    float *ema;          /* average, updated in place */
+    const float *p;      /* parameter or buffer of the trained model */
+    long n;              /* elements */
+} yolo_ema_tensor;
+/* One tensor. */
+int yolo_ema_update(float *ema, const float *p, long n, float w, const float *skip_flag, yolo_stream_t stream);
+/* A whole list (torch._foreach_lerp_): one launch per YOLO_MT_MAX tensors, the host table copied into the kernel arguments; empty
+ * tensors are legal. */
+int yolo_ema_update_multi(const yolo_ema_tensor *t, int count, float w, const float *skip_flag, yolo_stream_t stream);
+/* The same update as a BACKGROUND pass for a second stream, like yolo_sgd_step_multi_bg: `workgroups` (1 .. 256) persistent
+ * workgroups of 1024 threads, each holding one CU to itself.  At most YOLO_MT_MAX tensors. */
+int yolo_ema_update_multi_bg(const yolo_ema_tensor *t, int count, float w, const float *skip_flag, int workgroups,
+                             yolo_stream_t stream);
+
 /* g *= min(1, max_norm / (sqrt(*norm_sq) + 1e-6))  (stand-alone clip_grad_norm_ for other optimizers). */
 int yolo_clip_scale_f32(float *g, long n, const double *norm_sq, float max_norm, yolo_stream_t stream);
 

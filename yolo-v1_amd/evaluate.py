@@ -27,13 +27,17 @@ def main():
     ap.add_argument("--nms-threshold", type=float, default=0.4)
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--output", default="evaluation_results.txt")
+    ap.add_argument("--use-ema", action="store_true", help="evaluate the averaged weights of a train.py --ema-decay checkpoint (ema_state_dict)")
     a = ap.parse_args()
     ds = SyntheticYOLODataset(a.synthetic, seed=2) if a.synthetic else create_voc_datasets([("2007", "test")], augment=False)
     loader = DataLoader(ds, batch_size=a.batch_size, shuffle=False, num_workers=4)
     bb = YOLOv1Backbone() if a.backbone == "yolov1" else ResNetBackbone(pretrained=False)
     model = YOLOv1(backbone=bb, num_classes=20)
     if a.checkpoint:
-        model.load_state_dict(torch.load(a.checkpoint, map_location=a.device, weights_only=True)["model_state_dict"])
+        from yolo.training.checkpoints import weights_of
+        model.load_state_dict(weights_of(torch.load(a.checkpoint, map_location=a.device, weights_only=True), a.use_ema, a.checkpoint))
+    elif a.use_ema:
+        ap.error("--use-ema needs --checkpoint")
     model = model.to(a.device)
     res = evaluate_model(model, loader, a.device, num_classes=20, conf_threshold=a.conf_threshold, nms_threshold=a.nms_threshold)
     lines = [f"{k}: {float(v):.6f}" for k, v in res.items()]

@@ -19,12 +19,15 @@ from yolo.inference import YOLOInference  # noqa: E402
 from yolo.utils import VOC_CLASSES, draw_detections  # noqa: E402
 
 
-def load_model(checkpoint_path: str | None, device: str, num_classes: int = 20, backbone: str = "resnet50") -> YOLOv1:
+def load_model(checkpoint_path: str | None, device: str, num_classes: int = 20, backbone: str = "resnet50", use_ema: bool = False) -> YOLOv1:
     bb = YOLOv1Backbone() if backbone == "yolov1" else ResNetBackbone(pretrained=False)
     model = YOLOv1(backbone=bb, num_classes=num_classes)
     if checkpoint_path:
         ck = torch.load(checkpoint_path, map_location=device, weights_only=True)
-        model.load_state_dict(ck["model_state_dict"])
+        from yolo.training.checkpoints import weights_of
+        model.load_state_dict(weights_of(ck, use_ema, checkpoint_path))
+    elif use_ema:
+        raise SystemExit("--use-ema needs --checkpoint")
     return model.eval().to(device)
 
 
@@ -37,8 +40,9 @@ def main():
     ap.add_argument("--conf-threshold", type=float, default=0.5)
     ap.add_argument("--nms-threshold", type=float, default=0.4)
     ap.add_argument("--output-dir", default=None)
+    ap.add_argument("--use-ema", action="store_true", help="load the averaged weights of a train.py --ema-decay checkpoint (ema_state_dict)")
     a = ap.parse_args()
-    engine = YOLOInference(load_model(a.checkpoint, a.device, backbone=a.backbone), device=a.device)
+    engine = YOLOInference(load_model(a.checkpoint, a.device, backbone=a.backbone, use_ema=a.use_ema), device=a.device)
     for path in a.images:
         dets = engine.predict(path, conf_threshold=a.conf_threshold, nms_threshold=a.nms_threshold, class_names=VOC_CLASSES)
         print(f"{path}: {len(dets)} detections")

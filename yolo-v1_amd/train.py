@@ -66,6 +66,10 @@ def main():
     ap.add_argument("--voc-root", default=None, help="dataset root (default: $VOC_ROOT or ./data)")
     ap.add_argument("--deterministic", action="store_true",
                     help="EngineConfig.DETERMINISTIC: every order-dependent sum of the training step runs order-fixed (bit-reproducible steps and --resume)")
+    ap.add_argument("--ema-decay", type=float, default=None,
+                    help="keep an exponential moving average of the weights with this decay (e.g. 0.9999): it is what gets validated, and every "
+                         "checkpoint carries it as ema_state_dict (evaluate.py / predict.py --use-ema).  Default: no EMA")
+    ap.add_argument("--ema-tau", type=float, default=0.0, help="warm-up of --ema-decay: decay * (1 - exp(-updates / tau)); 0: none")
     ap.add_argument("--seed", type=int, default=None, help="seed of torch, numpy, random and the loaders (every epoch starts from (seed, epoch))")
     a = ap.parse_args()
     if a.deterministic:
@@ -145,6 +149,12 @@ def main():
             scheduler.load_state_dict(ck["scheduler_state_dict"])
         start_epoch = ck["epoch"] + 1
         best_val, best_map = ck.get("val_loss"), ck.get("mAP50:95")
+    ema = None
+    if a.ema_decay is not None:
+        from yolo.optim import ModelEMA
+        ema = ModelEMA(model, decay=a.ema_decay, tau=a.ema_tau, optimizer=optimizer if device == "cuda" else None)
+        if a.resume and "ema_state_dict" in ck:      # (a file without one: the average starts from the resumed weights, copied just above)
+            ema.load_state_dict({"module": ck["ema_state_dict"], "updates": ck.get("ema_updates", 0), "decay": a.ema_decay, "tau": a.ema_tau})
 
     ckdir = Path(a.checkpoint_dir)
     if rank == 0:
@@ -152,7 +162,7 @@ def main():
     res = training.train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, a.epochs, ckdir,
                          save_frequency=a.save_frequency, compute_map=a.compute_map, start_epoch=start_epoch,
                          best_val_loss_init=best_val, best_map_init=best_map, seed=a.seed,
-                         record={"seed": a.seed, "deterministic": bool(a.deterministic)} if a.seed is not None else None)
+                         record={"seed": a.seed, "deterministic": bool(a.deterministic)} if a.seed is not None else None, ema=ema)
     if rank == 0:
         print("done:", res)
     if world > 1:

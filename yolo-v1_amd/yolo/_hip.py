@@ -83,6 +83,12 @@ class SgdTensor(ctypes.Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("buf", c_void_p), ("p_bf16", c_void_p), ("n", ctypes.c_long)]
 
 
+class EmaTensor(ctypes.Structure):
+    """struct yolo_ema_tensor (include/yolo_hip.h)."""
+
+    _fields_ = [("ema", c_void_p), ("p", c_void_p), ("n", ctypes.c_long)]
+
+
 class ConvPackItem(ctypes.Structure):
     """struct yolo_conv_pack_item (include/yolo_hip.h)."""
 
@@ -180,6 +186,9 @@ _SIGS = {
     "yolo_sgd_step": [c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
     "yolo_sgd_step_multi": [ctypes.POINTER(SgdTensor), c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p],
     "yolo_sgd_step_multi_bg": [ctypes.POINTER(SgdTensor), c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p],
+    "yolo_ema_update": [c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p],
+    "yolo_ema_update_multi": [ctypes.POINTER(EmaTensor), c_int, c_float, c_void_p, c_void_p],
+    "yolo_ema_update_multi_bg": [ctypes.POINTER(EmaTensor), c_int, c_float, c_void_p, c_int, c_void_p],
     "yolo_bias_lrelu_rows": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "yolo_bias_lrelu_rows_slabs": [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
 }

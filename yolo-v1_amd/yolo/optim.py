@@ -19,7 +19,7 @@ import ctypes
 import os
 
 from . import _hip
-from ._hip import AdamTensor, SgdTensor, check, lib, ptr, stream
+from ._hip import AdamTensor, EmaTensor, SgdTensor, check, lib, ptr, stream
 from .config import CONFIG as CFG
 
 
@@ -28,6 +28,7 @@ BG_CUS = 128       # CUs the background update of the Linear layers holds (yolo_
                    # queue and so lose only the share of the chip the pass holds.  Step at batch 64 (tools/ab_train.py, one process): 32 CUs 12.16 ms,
                    # 48: 11.20, 64: 11.02-11.10, 96: 10.92, 128: 10.89-10.99, 160: 11.06, 192: 11.17, 256: 11.37.  (Round 2, statically scheduled conv
                    # kernels: 64 was the optimum and 96 no better.)
+EMA_BACKGROUND = True   # ModelEMA averages the parameters of a background update in the background too ("Weight EMA", has the step times)
 OVERLAP = os.environ.get("YOLO_ADAM_OVERLAP", "1") != "0"     # attach_plan(overlap=True) takes effect (switch for A/B runs)
 
 
@@ -138,6 +139,7 @@ class _Fused(torch.optim.Optimizer):
         # the step must update nothing.  The training loop hands over YOLOLoss's error word (LossParts.device_flag), which the host
         # reads only after the step was enqueued -- the reference raises inside the loss forward, before any update
         self.skip_if = None
+        self.last_skip = None                     # the skip_if the last step() consumed (None: it had none): ModelEMA.update hands it to its own launches
         self._hooked: set = set()                 # ids of the modules that carry this optimizer's state_dict / load_state_dict hooks
 
     @torch.no_grad()
@@ -167,6 +169,7 @@ class _Fused(torch.optim.Optimizer):
     def _step_on_device(self, all_params, loss):
         norm = grad_norm_sq(all_params, self._known_norms()) if self.max_grad_norm is not None else None
         skip, self.skip_if = self.skip_if, None
+        self.last_skip = skip
         if skip is not None:
             if not (skip.is_cuda and skip.dtype == torch.float32 and skip.numel() == 1):
                 raise ValueError("skip_if must be one float32 on the device")
@@ -300,6 +303,7 @@ class Adam(_Fused):
             total = float(grad_norm_sq(all_params, known).sqrt())
             clip = min(1.0, self.max_grad_norm / (total + 1e-6))
         skip, self.skip_if = self.skip_if, None
+        self.last_skip = skip
         if skip is not None and float(skip) != 0.0:
             return
         for group in self.param_groups:
@@ -371,6 +375,7 @@ class SGD(_Fused):
             total = grad_norm_sq(all_params, known).sqrt().float()
             clip = (torch.tensor(self.max_grad_norm, dtype=torch.float32) / (total + torch.tensor(1e-6, dtype=torch.float32))).clamp(max=1.0)
         skip, self.skip_if = self.skip_if, None
+        self.last_skip = skip
         if skip is not None and float(skip) != 0.0:
             return
         for group in self.param_groups:
@@ -413,3 +418,174 @@ class SGD(_Fused):
             check(lib().yolo_sgd_step_multi_bg(tab, count, *h, BG_CUS, ctypes.c_void_p(side.cuda_stream)), "yolo_sgd_step_multi_bg")
         else:
             check(lib().yolo_sgd_step_multi(tab, count, *h, stream()), "yolo_sgd_step_multi")
+
+
+def _state_tensors(module):
+    """(name, tensor) of every entry ``module.state_dict()`` would hold, in its order (per module: parameters, persistent buffers, then the
+    children) -- read off the modules themselves, because ``state_dict()`` runs the hooks that wait for a background update (_Fused._hook_owner)
+    and ModelEMA.update must not wait"""
+    for prefix, m in module.named_modules(remove_duplicate=False):
+        dot = prefix + "." if prefix else ""
+        for k, v in m._parameters.items():
+            if v is not None:
+                yield dot + k, v
+        for k, v in m._buffers.items():
+            if v is not None and k not in m._non_persistent_buffers_set:
+                yield dot + k, v
+
+
+class ModelEMA:
+    """Exponential moving average of a model's weights, the copy a detector validates and ships (torch.optim.swa_utils.AveragedModel with
+    get_ema_multi_avg_fn): ``module`` is a deep copy of ``model`` in eval() mode, and every ``update()`` -- one per optimizer step -- moves it
+    towards the model,
+
+        e = fmaf(w, p - e, e)          w = fp32(1 - d),  d = decay * (1 - exp(-updates / tau)) if tau > 0 else decay
+
+    for floating-point parameters and buffers (BatchNorm running statistics); other buffers (num_batches_tracked) are copied.  CPU tensors
+    take ``torch._foreach_lerp_``, device tensors yolo_ema_update_multi (ema.hip) on the current stream.
+
+    ``optimizer``: the ``yolo.optim`` optimizer that steps ``model``.  The parameters it updates in the background
+    (``attach_plan(plan, overlap=True)``: the Linear layers, three quarters of the bytes) are averaged in the background too:
+    yolo_ema_update_multi_bg on the optimizer's own second stream, behind its launch, on BG_CUS CUs beside the next forward's conv stack.
+    A step the optimizer skipped on the device (``skip_if``) is no EMA step: its flag goes to the EMA launches as well.
+
+    Nobody who reads ``module`` has to know about that stream: ``state_dict()`` / ``load_state_dict()`` here and on ``module``,
+    ``copy.deepcopy(module)`` and a forward of ``module`` make the current stream wait for the background launch by themselves (the hooks and
+    the plan's ``params_ready`` slot that ``attach_plan`` uses on the model's side); ``synchronize()`` does it for any other reader.
+    ``background=False`` keeps every launch on the current stream, which then waits for the optimizer's background launch first (default:
+    EMA_BACKGROUND).  Without ``optimizer`` nothing is known about a second stream: give it whenever the optimizer has one."""
+
+    def __init__(self, model, decay: float = 0.9999, tau: float = 0.0, optimizer=None, background: bool | None = None):
+        import copy
+        if not (0.0 <= decay <= 1.0) or tau < 0.0:
+            raise ValueError("ModelEMA needs 0 <= decay <= 1 and tau >= 0")
+        self.decay, self.tau, self.updates = float(decay), float(tau), 0
+        self.optimizer = optimizer
+        self.background = EMA_BACKGROUND if background is None else bool(background)
+        self.module = copy.deepcopy(model).eval()       # waits for a background update of ``model`` (models._PlanOwner.__deepcopy__)
+        self.module.requires_grad_(False)
+        import weakref
+        self._model = weakref.ref(model)
+        self._event, self._event_device = None, None    # behind the last background launch
+        self._hooked: set = set()
+        self._hook(self.module)
+
+    def _hook(self, mod) -> None:
+        if id(mod) in self._hooked:
+            return
+        self._hooked.add(id(mod))
+        import weakref
+        me = weakref.ref(self)
+
+        def wait(*_a, **_k):
+            ema = me()
+            if ema is not None:
+                ema.synchronize()
+        mod.register_state_dict_pre_hook(wait)
+        mod.register_load_state_dict_pre_hook(wait)
+
+    def effective_decay(self, updates: int | None = None) -> float:
+        """the decay of update number ``updates`` (default: the last one made): the warm-up of ``tau`` lets the first updates follow the model"""
+        import math
+        n = self.updates if updates is None else updates
+        return self.decay * (1.0 - math.exp(-n / self.tau)) if self.tau > 0 else self.decay
+
+    def synchronize(self) -> None:
+        """make the CURRENT stream wait for a background update of ``module`` still running on the optimizer's second stream"""
+        if self._event is not None:
+            torch.cuda.current_stream(self._event_device).wait_event(self._event)
+            self._event = None
+
+    @torch.no_grad()
+    def update(self, model=None) -> None:
+        """one EMA step from ``model`` (default: the model the constructor copied), to be called after ``optimizer.step()``.  The host counts
+        it in ``updates`` even when the device-side flag then cancels it: the training loop ends at such a step, where the loss raises."""
+        model = self._model() if model is None else model
+        if model is None:
+            raise ValueError("ModelEMA.update: the model the average was built from is gone, pass the one being trained")
+        opt = self.optimizer
+        skip = getattr(opt, "last_skip", None)
+        dst, src = list(_state_tensors(self.module)), list(_state_tensors(model))
+        if [n for n, _ in dst] != [n for n, _ in src]:
+            raise RuntimeError("ModelEMA.update: the model's state_dict entries are not those of the averaged copy")
+        if skip is not None and not skip.is_cuda and float(skip) != 0.0:
+            return                                      # CPU run: the optimizer read the flag on the host and skipped; so does the EMA
+        self.updates += 1
+        w = 1.0 - self.effective_decay()                # in double; the launches narrow it to fp32, the value tests/ema_ref.py works with
+        cpu_e, cpu_p, fore, back = [], [], [], []
+        deferred = opt.deferred if (self.background and opt is not None and OVERLAP and getattr(opt, "_side", None) is not None) else {}
+        for (name, e), (_, p) in zip(dst, src):
+            if e.shape != p.shape or e.device != p.device:
+                raise RuntimeError(f"ModelEMA.update: {name}: {tuple(p.shape)} on {p.device} does not match the averaged copy")
+            if not e.is_floating_point():
+                if skip is None or not e.is_cuda:
+                    e.copy_(p)
+                else:
+                    e.copy_(torch.where(skip != 0, e, p))      # a skipped step is no EMA step: the counter stays, too
+            elif e.numel() == 0:
+                continue
+            elif not e.is_cuda:
+                cpu_e.append(e)
+                cpu_p.append(p.detach().to(e.dtype))
+            else:
+                if e.dtype != torch.float32 or p.dtype != torch.float32 or not (e.is_contiguous() and p.is_contiguous()):
+                    raise RuntimeError(f"yolo.optim.ModelEMA needs contiguous fp32 tensors on the device ({name})")
+                (back if id(p) in deferred else fore).append((e, p))
+        if cpu_e:
+            torch._foreach_lerp_(cpu_e, cpu_p, w)
+        if not (fore or back):
+            return
+        if len(back) > 48:                              # more than one background table: the optimizer took the foreground as well
+            fore, back = fore + back, []
+        if not back and hasattr(opt, "synchronize"):
+            opt.synchronize()                           # everything in the foreground: the optimizer's background launch writes p, wait for it
+        dev = (fore or back)[0][0].device
+        _hip.require_cuda(skip, *[t for pair in fore + back for t in pair])
+        with torch.cuda.device(dev):
+            if fore:
+                self.synchronize()                      # these may include tensors an earlier update left to the second stream (long done by now)
+                tab = (EmaTensor * len(fore))(*[EmaTensor(e.data_ptr(), p.data_ptr(), e.numel()) for e, p in fore])
+                check(lib().yolo_ema_update_multi(tab, len(fore), w, ptr(skip), stream()), "yolo_ema_update_multi")   # one launch per 48 tensors
+            if back:
+                # The second stream runs its launches in order.  The optimizer's background launch of this step is already on it, so the
+                # EMA reads the updated p; the NEXT step's background launch -- the only writer of these p -- will be enqueued on the same
+                # stream behind this read.  What the main stream did to the averaged tensors (a forward of ``module`` during validation,
+                # load_state_dict) comes first through wait_stream; later readers there wait for the event recorded below.
+                side = opt._side
+                side.wait_stream(torch.cuda.current_stream())
+                for e, _ in back:
+                    e.record_stream(side)
+                if skip is not None:
+                    skip.record_stream(side)
+                tab = (EmaTensor * len(back))(*[EmaTensor(e.data_ptr(), p.data_ptr(), e.numel()) for e, p in back])
+                check(lib().yolo_ema_update_multi_bg(tab, len(back), w, ptr(skip), BG_CUS, ctypes.c_void_p(side.cuda_stream)),
+                      "yolo_ema_update_multi_bg")
+                ev = torch.cuda.Event()
+                ev.record(side)
+                self._event, self._event_device = ev, dev
+                self._publish(model, ev)
+            for e, _ in fore + back:
+                # the kernels wrote through raw pointers: bump the version so that ``module``'s engine plan repacks its bf16 operands
+                torch.autograd.graph.increment_version(e)
+
+    def _publish(self, model, ev) -> None:
+        """hand the event to the averaged copy's own plans (the twins of the plans whose Linear layers the optimizer defers): their forward
+        waits for it in front of the first Linear layer, and a deep copy of their owner waits too"""
+        names = {id(m): n for n, m in model.named_modules()}
+        for plan in {id(pl): pl for pl in self.optimizer.deferred.values()}.values():
+            owner = plan.owner() if getattr(plan, "owner", None) is not None else None
+            if owner is None or id(owner) not in names:
+                continue
+            twin = self.module.get_submodule(names[id(owner)])
+            self._hook(twin)
+            twin_plan = twin.__dict__.get("_plan")
+            if twin_plan is not None and hasattr(twin_plan, "params_ready"):
+                twin_plan.params_ready.event = ev
+
+    def state_dict(self) -> dict:
+        return {"module": self.module.state_dict(), "updates": self.updates, "decay": self.decay, "tau": self.tau}
+
+    def load_state_dict(self, state: dict) -> None:
+        self.module.load_state_dict(state["module"])
+        self.updates = int(state["updates"])
+        self.decay, self.tau = float(state.get("decay", self.decay)), float(state.get("tau", self.tau))

@@ -23,8 +23,9 @@ _PARTS = ("total", "coord", "conf_obj", "conf_noobj", "class")
 _CLIP = 10.0
 
 
-def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, writer=None, scaler=None) -> dict[str, float]:
-    """One pass over ``dataloader``; returns the mean of each loss component.
+def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, writer=None, scaler=None, ema=None) -> dict[str, float]:
+    """One pass over ``dataloader``; returns the mean of each loss component.  ``ema``: a ``yolo.optim.ModelEMA`` of ``model``, moved after every
+    optimizer step (on a device it is enqueued like the step itself, nothing waits).
 
     ``scaler`` (the reference's fp16 autocast + GradScaler branch, trainer.py:69-83) is accepted and not used: on a ROCm
     device the engine already computes in bf16 with fp32 accumulation and fp32 master weights, which needs no loss scaling;
@@ -57,6 +58,8 @@ def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, wri
             # the read of `parts` below; the reference raises inside the loss, before any update)
             optimizer.skip_if = getattr(parts, "device_flag", None)
         optimizer.step()
+        if ema is not None:
+            ema.update(model)
         for k in _PARTS:
             sums[k] += parts[k]
         n += 1
@@ -110,13 +113,17 @@ def seed_epoch(seed: int, epoch: int, train_loader=None) -> None:
 def train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, num_epochs: int, checkpoint_dir,
           save_frequency: int = 5, writer=None, compute_map: bool = False, map_frequency: int = 5, num_classes: int = 20,
           start_epoch: int = 1, best_val_loss_init: float = None, best_map_init: float = None, scaler=None,
-          seed: int | None = None, record: dict | None = None) -> dict[str, float]:
+          seed: int | None = None, record: dict | None = None, ema=None) -> dict[str, float]:
     """Epoch loop with the reference's checkpoint policy: latest every epoch, every ``save_frequency``
     epochs, best validation loss, best mAP50:95.
 
     ``seed``: every epoch starts from generators seeded by (seed, epoch) -- torch (host and device: the dropout masks), numpy, ``random`` and
     the train loader's shuffling generator -- so epoch e of a resumed run draws what epoch e of the uninterrupted run drew, and no generator
-    state has to travel in the checkpoint.  ``record``: extra plain entries for the epoch checkpoints (train.py: seed, deterministic)."""
+    state has to travel in the checkpoint.  ``record``: extra plain entries for the epoch checkpoints (train.py: seed, deterministic).
+
+    ``ema``: a ``yolo.optim.ModelEMA`` of ``model``: updated after every step, and the copy that is validated -- best-loss and best-mAP selection
+    follow the averaged weights.  Every checkpoint then carries them next to the raw ones (checkpoints.py).  With several ranks each keeps its own
+    average; they are identical because the parameters are, and nothing is communicated."""
     best_val = float("inf") if best_val_loss_init is None else best_val_loss_init
     best_map = 0.0 if best_map_init is None else best_map_init
     final_train = None
@@ -124,10 +131,10 @@ def train(model, train_loader, val_loader, criterion, optimizer, scheduler, devi
         print(f"\n===== Epoch {epoch}/{num_epochs} =====")
         if seed is not None:
             seed_epoch(seed, epoch, train_loader)
-        tr = train_epoch(model, train_loader, criterion, optimizer, device, epoch, writer, scaler)
+        tr = train_epoch(model, train_loader, criterion, optimizer, device, epoch, writer, scaler, ema=ema)
         print("  train:", {k: round(v, 4) for k, v in tr.items()})
         want_map = compute_map and (epoch % map_frequency == 0 or epoch == num_epochs)
-        va = validate(model, val_loader, criterion, device, compute_map=want_map, num_classes=num_classes)
+        va = validate(model if ema is None else ema.module, val_loader, criterion, device, compute_map=want_map, num_classes=num_classes)
         print("  val:  ", {k: round(float(v), 4) for k, v in va.items()})
         scheduler.step()
         lr = optimizer.param_groups[0]["lr"]
@@ -142,17 +149,17 @@ def train(model, train_loader, val_loader, criterion, optimizer, scheduler, devi
         # ranks wait, so that nobody runs ahead of a file that a later --resume on all ranks would read
         writer_rank = not (dist.is_available() and dist.is_initialized()) or dist.get_rank() == 0
         if writer_rank:
-            save_checkpoint(checkpoint_dir / "yolo_latest.pth", epoch, model, optimizer, scheduler, tr, va, record)
+            save_checkpoint(checkpoint_dir / "yolo_latest.pth", epoch, model, optimizer, scheduler, tr, va, record, ema=ema)
             if epoch % save_frequency == 0:
-                save_checkpoint(checkpoint_dir / f"yolo_epoch_{epoch}.pth", epoch, model, optimizer, scheduler, tr, va, record)
+                save_checkpoint(checkpoint_dir / f"yolo_epoch_{epoch}.pth", epoch, model, optimizer, scheduler, tr, va, record, ema=ema)
         if va["total"] < best_val:
             best_val = va["total"]
             if writer_rank:
-                save_best_model(checkpoint_dir / "yolo_best.pth", epoch, model, optimizer, va, "val_loss", best_val)
+                save_best_model(checkpoint_dir / "yolo_best.pth", epoch, model, optimizer, va, "val_loss", best_val, ema=ema)
         if "mAP50:95" in va and va["mAP50:95"] > best_map:
             best_map = va["mAP50:95"]
             if writer_rank:
-                save_best_map_model(checkpoint_dir / "yolo_best_map.pth", epoch, model, optimizer, va, best_map)
+                save_best_map_model(checkpoint_dir / "yolo_best_map.pth", epoch, model, optimizer, va, best_map, ema=ema)
         if dist.is_available() and dist.is_initialized():
             dist.barrier()
         final_train = tr["total"]
