@@ -533,6 +533,27 @@ int yolo_ema_update_multi(const yolo_ema_tensor *t, int count, float w, const fl
 int yolo_ema_update_multi_bg(const yolo_ema_tensor *t, int count, float w, const float *skip_flag, int workgroups,
                              yolo_stream_t stream);
 
+/* Gradient accumulation, K micro-batches per optimizer step: replaces what autograd's AccumulateGrad does when backward() runs again
+ * without zero_grad (one stock add per tensor, no 1/K), and torch._foreach_mul_ / torch._foreach_add_(acc, grads, alpha=1/K) (the
+ * reference has no accumulation: src/yolo/training/trainer.py:64 clears the gradients in front of every backward).  Per element, in fp32:
+ *     dst = fmaf(alpha, x, y)           y != NULL;      alpha = (float)(1.0 / K), formed by the host in double
+ *     dst = alpha * x                   y == NULL
+ * -- one rounding either way (the product inside the fma is exact); both forms compute the same bits.  x and y are only read, unless dst IS
+ * one of them: dst == x or dst == y exactly is the in-place use (acc = fmaf(alpha, g, acc); the fold g = fmaf(alpha, g, acc)), every element
+ * read before it is written by the same lane.  *skip_flag != 0 (device float, NULL: none) writes nothing.
+ * YOLO_E_ARG: null dst or x, n < 0, count < 0, alpha not finite.  YOLO_E_UNSUPPORTED: a pointer not 16-B aligned, dst overlapping x or y
+ * without being it.  Every tensor is checked before the first launch: a refused call launches nothing. */
+typedef struct yolo_accum_tensor {
+    float *dst;          /* written; may be x or y */
+    const float *x;      /* the micro-batch's gradient */
+    const float *y;      /* the accumulator so far, or NULL */
+    long n;              /* elements */
+} yolo_accum_tensor;
+/* One tensor. */
+int yolo_grad_accum(float *dst, const float *x, const float *y, long n, float alpha, const float *skip_flag, yolo_stream_t stream);
+/* A whole list: one launch per YOLO_MT_MAX tensors, the host table copied into the kernel arguments; empty tensors are legal. */
+int yolo_grad_accum_multi(const yolo_accum_tensor *t, int count, float alpha, const float *skip_flag, yolo_stream_t stream);
+
 /* g *= min(1, max_norm / (sqrt(*norm_sq) + 1e-6))  (stand-alone clip_grad_norm_ for other optimizers). */
 int yolo_clip_scale_f32(float *g, long n, const double *norm_sq, float max_norm, yolo_stream_t stream);
 

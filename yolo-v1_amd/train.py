@@ -70,8 +70,13 @@ def main():
                     help="keep an exponential moving average of the weights with this decay (e.g. 0.9999): it is what gets validated, and every "
                          "checkpoint carries it as ema_state_dict (evaluate.py / predict.py --use-ema).  Default: no EMA")
     ap.add_argument("--ema-tau", type=float, default=0.0, help="warm-up of --ema-decay: decay * (1 - exp(-updates / tau)); 0: none")
+    ap.add_argument("--accum-steps", type=int, default=1,
+                    help="gradient accumulation: K batches per optimizer step and per all-reduce -- effective batch = batch-size x K x world; a last "
+                         "group of an epoch with fewer than K batches is dropped.  Default 1: none")
     ap.add_argument("--seed", type=int, default=None, help="seed of torch, numpy, random and the loaders (every epoch starts from (seed, epoch))")
     a = ap.parse_args()
+    if a.accum_steps < 1:
+        ap.error("--accum-steps must be at least 1")
     if a.deterministic:
         if a.backbone == "resnet50":
             # (the training loop puts the whole model in train(): there is no eval-mode trunk to ask for here)
@@ -130,8 +135,10 @@ def main():
             optimizer = Adam(params, lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=10.0)
         if model._fusable():
             # the Linear layers' update runs as a background pass beside the next forward's conv stack (11.40 vs 11.58 ms per step
-            # at batch 64: the persistent conv kernels draw their tiles from a queue, so the held CUs cost only their share)
-            optimizer.attach_plan(model.hip_plan(), overlap=True)
+            # at batch 64: the persistent conv kernels draw their tiles from a queue, so the held CUs cost only their share).  With
+            # --accum-steps K > 1 the update stays in the foreground: one step per K batches leaves one forward in K to hide it under, and
+            # beside the gradient arena the background form measured slower (13.04 vs 10.53 ms per batch at K = 4)
+            optimizer.attach_plan(model.hip_plan(), overlap=a.accum_steps == 1)
         elif hasattr(model.head, "hip_plan"):          # DetectionHead on a ResNet trunk: its Linear layers' bf16 operands
             optimizer.attach_plan(model.head.hip_plan())
     elif a.optimizer == "sgd":
@@ -159,10 +166,14 @@ def main():
     ckdir = Path(a.checkpoint_dir)
     if rank == 0:
         ckdir.mkdir(parents=True, exist_ok=True)
+    record = {"seed": a.seed, "deterministic": bool(a.deterministic)} if a.seed is not None else None
+    extra = {}
+    if a.accum_steps > 1:          # (1: the call, and the checkpoint's keys, are those of a run without the option)
+        record = {**(record or {}), "accum_steps": a.accum_steps}
+        extra["accum_steps"] = a.accum_steps
     res = training.train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, a.epochs, ckdir,
                          save_frequency=a.save_frequency, compute_map=a.compute_map, start_epoch=start_epoch,
-                         best_val_loss_init=best_val, best_map_init=best_map, seed=a.seed,
-                         record={"seed": a.seed, "deterministic": bool(a.deterministic)} if a.seed is not None else None, ema=ema)
+                         best_val_loss_init=best_val, best_map_init=best_map, seed=a.seed, record=record, ema=ema, **extra)
     if rank == 0:
         print("done:", res)
     if world > 1:

@@ -89,6 +89,12 @@ class EmaTensor(ctypes.Structure):
     _fields_ = [("ema", c_void_p), ("p", c_void_p), ("n", ctypes.c_long)]
 
 
+class AccumTensor(ctypes.Structure):
+    """struct yolo_accum_tensor (include/yolo_hip.h)."""
+
+    _fields_ = [("dst", c_void_p), ("x", c_void_p), ("y", c_void_p), ("n", ctypes.c_long)]
+
+
 class ConvPackItem(ctypes.Structure):
     """struct yolo_conv_pack_item (include/yolo_hip.h)."""
 
@@ -189,6 +195,8 @@ _SIGS = {
     "yolo_ema_update": [c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p],
     "yolo_ema_update_multi": [ctypes.POINTER(EmaTensor), c_int, c_float, c_void_p, c_void_p],
     "yolo_ema_update_multi_bg": [ctypes.POINTER(EmaTensor), c_int, c_float, c_void_p, c_int, c_void_p],
+    "yolo_grad_accum": [c_void_p, c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p],
+    "yolo_grad_accum_multi": [ctypes.POINTER(AccumTensor), c_int, c_float, c_void_p, c_void_p],
     "yolo_bias_lrelu_rows": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "yolo_bias_lrelu_rows_slabs": [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
 }

@@ -95,7 +95,8 @@ class Plan:
 
     def attach_grad_arena(self, device) -> torch.Tensor:
         """Allocate the gradient arena; backward then writes gradients into it, assigns ``p.grad`` views and
-        returns no gradients to autograd (gradients are OVERWRITTEN each backward: no accumulation)."""
+        returns no gradients to autograd (gradients are OVERWRITTEN each backward; yolo.optim.GradAccumulator keeps the sum of several
+        backward passes beside the arena and folds it back into it)."""
         order = [li for li in reversed(range(len(self.layers))) if self.layers[li].kind in ("conv", "fc")]
         off = 0
         wv, bv = {}, {}

@@ -19,7 +19,7 @@ import ctypes
 import os
 
 from . import _hip
-from ._hip import AdamTensor, EmaTensor, SgdTensor, check, lib, ptr, stream
+from ._hip import AccumTensor, AdamTensor, EmaTensor, SgdTensor, check, lib, ptr, stream
 from .config import CONFIG as CFG
 
 
@@ -589,3 +589,196 @@ class ModelEMA:
         self.module.load_state_dict(state["module"])
         self.updates = int(state["updates"])
         self.decay, self.tau = float(state.get("decay", self.decay)), float(state.get("tau", self.tau))
+
+
+def accum_alpha(steps: int) -> float:
+    """the fp32 weight of one micro-batch in a group of ``steps``, as a Python float: (float)(1.0 / steps), the quotient formed in double"""
+    return float(torch.tensor(1.0 / int(steps), dtype=torch.float64).float())
+
+
+def _reducers(reducer) -> list:
+    """the reducers behind ``reducer`` (parallel._Both holds several)"""
+    if reducer is None:
+        return []
+    if hasattr(reducer, "reducers"):
+        return [r for sub in reducer.reducers for r in _reducers(sub)]
+    return [reducer]
+
+
+class GradAccumulator:
+    """Gradient accumulation: ``steps`` = K micro-batches per optimizer step, and per all-reduce (DDP's ``no_sync``, Darknet's subdivisions).
+    After the K-th backward ``p.grad`` holds
+
+        g = (g_1 + ... + g_K) / K          as the chain  a = alpha g_1;  a = fmaf(alpha, g_k, a);  g = fmaf(alpha, g_K, a),   alpha = fp32(1 / K)
+
+    -- the gradient of the concatenated batch, because YOLOLoss divides by the local N and the micro-batches are equal.  The last link
+    folds the accumulator INTO THE GRADIENT MEMORY, not the other way round: ``p.grad`` stays the arena view (or autograd's tensor), so the
+    optimizers, the clip norm, the bf16 shadows, the background update of the Linear layers and the reducers read what they read without
+    accumulation, and none of them changes.
+
+        acc = GradAccumulator(model, K, reducer)          # reducer: parallel.make_grad_reducer(model, device), or None
+        for images, targets in loader:
+            optimizer.zero_grad(set_to_none=True)
+            acc.before_backward()
+            loss, parts = criterion(model(images), targets)
+            loss.backward()
+            if acc.after_backward(getattr(parts, "device_flag", None)):
+                optimizer.skip_if = acc.skip_if
+                optimizer.step()
+
+    On a GPU, a fused YOLOv1 (``model._fusable()``) or a ``DetectionHead`` with ``hip_plan`` gets the plan's gradient arena attached if it has
+    none (the plan's ``on_*`` callbacks stay None without a reducer) and ONE flat accumulator of the arena's size: the whole network is one
+    yolo_grad_accum call per micro-batch (accum.hip; 8 B per element for the first, 12 B for the others).  Parameters outside a plan (a ResNet
+    trunk, custom modules) get an accumulator each and go through yolo_grad_accum_multi.  CPU tensors take stock torch ops
+    (``torch._foreach_mul_`` / ``torch._foreach_add_`` with alpha).  ``steps == 1`` allocates nothing and launches nothing.
+
+    ``skip_if``: the maximum of the micro-batches' ``LossParts.device_flag`` (a torch op on the device, nothing waits): one flagged micro-batch
+    cancels the group's optimizer step, and through ``optimizer.last_skip`` the EMA step.
+
+    With a reducer, ``before_backward`` mutes it for the micro-batches 1 .. K-1 (no range announced, no collective enqueued, ``all_reduce_mean``
+    not called), so the ranks exchange one gradient per K backward passes.  For a ``parallel.OverlappedGradAllReduce`` the fold of the K-th
+    pass is its ``pre_reduce(lo, hi)`` hook: ``arena[lo:hi]`` is folded immediately in front of the collective that carries it, on the stream
+    that enqueues the collective, so the all-reduce still overlaps the backward pass.  Why that is ordered:
+
+    * the ranges ``_reduce`` sees partition [0, arena.numel()) exactly once per backward, so every element is folded once;
+    * every range starts on a 256-B boundary (``attach_grad_arena`` rounds to 64 elements), which the kernel's 16-B rule needs;
+    * ``_check_ordered`` has verified that the enqueuing stream holds every piece of the range, so the fold reads a finished micro-gradient;
+    * the accumulator itself was written by the launches of the micro-batches 1 .. K-1 on the MAIN stream, each behind its own backward (whose
+      end joins the side stream into the main one).  The K-th backward enters the side stream through ``_on_side_stream``, which makes it
+      wait for everything queued on the main stream -- those launches included -- so a fold on either stream reads the finished sum.  The next
+      group's first launch overwrites the accumulator on the main stream behind the K-th backward's join, i.e. behind every fold.
+
+    After the fold the plans' ``grad_norm_sq`` hints are dropped and the arena's version is bumped (as ``OverlappedGradAllReduce.finish``
+    does): the hint is the last micro-gradient's norm, so the clip pass reads the folded gradient instead.  The pass is elementwise, so
+    ``EngineConfig.DETERMINISTIC`` keeps its promise with accumulation on."""
+
+    def __init__(self, model, steps: int, reducer=None):
+        if int(steps) != steps or steps < 1:
+            raise ValueError("GradAccumulator needs steps >= 1")
+        self.steps, self.reducer, self.micro = int(steps), reducer, 0
+        self.alpha = accum_alpha(self.steps)
+        self.skip_if = None                  # device float: the group's flag so far (None: no micro-batch brought one)
+        self._overlapped = [r for r in _reducers(reducer) if hasattr(r, "pre_reduce")]
+        self._arenas: list[tuple] = []       # (plan, accumulator of the arena's size, folded by a reducer's hook?)
+        self._rest: list = []                # parameters outside every plan
+        self._acc: dict[int, torch.Tensor] = {}      # id(param) -> accumulator, allocated at the parameter's first gradient
+        self._have: set = set()              # ids whose accumulator holds something in this group
+        if self.steps == 1:
+            return
+        params = [p for p in model.parameters() if p.requires_grad]
+        plans = {id(r.plan): (r.plan, r) for r in self._overlapped}
+        on_gpu = bool(params) and params[0].is_cuda
+        if on_gpu:
+            head = getattr(model, "head", None)
+            plan = model.hip_plan() if (hasattr(model, "_fusable") and model._fusable()) else \
+                head.hip_plan() if (head is not None and hasattr(head, "hip_plan")) else None
+            if plan is not None:
+                if plan.arena is None:
+                    plan.attach_grad_arena(params[0].device)
+                plans.setdefault(id(plan), (plan, None))
+        covered = set()
+        for plan, red in plans.values():
+            self._arenas.append((plan, torch.empty_like(plan.arena), red is not None))
+            covered |= {id(p) for p in plan.params}
+            if red is not None:
+                red.pre_reduce = self._hook(len(self._arenas) - 1)
+        self._rest = [p for p in params if id(p) not in covered]
+
+    # ------------------------------------------------------------------ the one operation, by device
+    def _run(self, items) -> None:
+        """items: (dst, x, y | None) tensors of one device, dst being x, y or neither -- dst = alpha * x (+ y)"""
+        if not items:
+            return
+        if not items[0][0].is_cuda:
+            store = [(d, x) for d, x, y in items if y is None and d is not x]
+            scale = [d for d, x, y in items if d is x]                                # the fold (and a fold without a sum: alpha * g)
+            if store:
+                torch._foreach_copy_([d for d, _ in store], [x for _, x in store])
+                scale += [d for d, _ in store]
+            if scale:
+                torch._foreach_mul_(scale, self.alpha)
+            fold = [(d, y) for d, x, y in items if d is x and y is not None]
+            if fold:
+                torch._foreach_add_([d for d, _ in fold], [y for _, y in fold])
+            add = [(d, x) for d, x, y in items if d is y]
+            if add:
+                torch._foreach_add_([d for d, _ in add], [x for _, x in add], alpha=self.alpha)
+            return
+        for t in items:
+            for v in t:
+                if v is not None and not (v.dtype == torch.float32 and v.is_contiguous()):
+                    raise RuntimeError("yolo.optim.GradAccumulator needs contiguous fp32 gradients on the device")
+        _hip.require_cuda(*[v for t in items for v in t if v is not None])
+        with torch.cuda.device(items[0][0].device):
+            if len(items) == 1:
+                dst, x, y = items[0]
+                check(lib().yolo_grad_accum(ptr(dst), ptr(x), ptr(y), dst.numel(), self.alpha, None, stream()), "yolo_grad_accum")
+            else:
+                tab = (AccumTensor * len(items))(*[AccumTensor(d.data_ptr(), x.data_ptr(), y.data_ptr() if y is not None else None, d.numel())
+                                                   for d, x, y in items])
+                check(lib().yolo_grad_accum_multi(tab, len(items), self.alpha, None, stream()), "yolo_grad_accum_multi")   # one launch per 48 tensors
+
+    def _hook(self, k: int):
+        def fold(lo: int, hi: int):
+            plan, acc, _ = self._arenas[k]
+            if self.micro == self.steps - 1:             # armed: the K-th backward of the group is running
+                g = plan.arena[lo:hi]
+                self._run([(g, g, acc[lo:hi])])
+        return fold
+
+    # ------------------------------------------------------------------ the two calls around loss.backward()
+    def before_backward(self) -> None:
+        """in front of every ``loss.backward()``: mutes the reducer on the micro-batches 1 .. K-1, arms the fold on the K-th"""
+        if self.micro == 0:
+            self.skip_if = None
+        last = self.micro == self.steps - 1
+        for r in self._overlapped:
+            r.muted = not last
+
+    @torch.no_grad()
+    def after_backward(self, device_flag=None) -> bool:
+        """behind every ``loss.backward()``: accumulates, and on the K-th call of a group folds (and averages across ranks) and returns True --
+        the optimizer's turn.  ``device_flag``: the loss's ``LossParts.device_flag`` (None: none)"""
+        if device_flag is not None:
+            self.skip_if = device_flag if self.skip_if is None else torch.maximum(self.skip_if, device_flag)
+        first, last = self.micro == 0, self.micro == self.steps - 1
+        self.micro = 0 if last else self.micro + 1
+        if self.steps == 1:
+            if self.reducer is not None:
+                self.reducer.all_reduce_mean()
+            return True
+        items = []
+        for plan, acc, hooked in self._arenas:
+            if not last:
+                items.append((acc, plan.arena, None if first else acc))
+            elif not hooked:
+                items.append((plan.arena, plan.arena, acc))
+        if first:
+            self._have.clear()
+        for p in self._rest:
+            g, a = p.grad, self._acc.get(id(p))
+            if g is None:
+                if last and id(p) in self._have:
+                    p.grad = a.clone()                   # no gradient in the last micro-batch: the sum so far is the group's
+                continue
+            if a is None and not last:
+                a = self._acc[id(p)] = torch.empty_like(g, memory_format=torch.contiguous_format)
+            have = id(p) in self._have
+            if not last:
+                items.append((a, g, a if have else None))
+                self._have.add(id(p))
+            else:
+                items.append((g, g, a if have else None))
+        by_dev: dict = {}
+        for it in items:
+            by_dev.setdefault(it[0].device, []).append(it)
+        for group in by_dev.values():
+            self._run(group)
+        if not last:
+            return False
+        if self.reducer is not None:
+            self.reducer.all_reduce_mean()           # an overlapped reducer folded range by range in front of its collectives
+        for plan, _, _ in self._arenas:
+            plan.grad_norm_sq.clear()                # the last micro-gradient's norm, not the group's
+            torch.autograd.graph.increment_version(plan.arena)
+        return True

@@ -72,7 +72,12 @@ class OverlappedGradAllReduce:
     all-reduce of that slice is enqueued; RCCL runs it on its own stream behind the kernels already queued
     and beside the rest of the conv backward.  ``finish()`` (call it between ``backward()`` and the
     optimizer) reduces the tail + the bias region and waits.  xGMI is point-to-point, so buckets are
-    large (default 64 MB) and few."""
+    large (default 64 MB) and few.
+
+    Gradient accumulation (``yolo.optim.GradAccumulator``) uses two switches.  ``muted = True``: the backward passes of the micro-batches
+    1 .. K-1 announce no range and enqueue no collective (``finish()`` is not called for them).  ``pre_reduce(lo, hi)``: called in front of
+    every collective, on the stream it is enqueued from -- the accumulator folds ``arena[lo:hi]`` there, so the all-reduce of the K-th
+    backward still overlaps that backward and carries the whole group's gradient."""
 
     def __init__(self, plan, device, bucket_bytes: int = 64 << 20, group=None, stream_id=None):
         self.plan = plan
@@ -95,8 +100,12 @@ class OverlappedGradAllReduce:
         self._pieces: list[tuple] = []        # (lo, hi, producing stream, tick) of the ranges announced in this backward pass
         self._waits: dict[tuple, int] = {}    # (waiter, waited) -> tick of the last wait
         self.log: list | None = None          # tests: (lo, hi, stream at the call, pieces) per enqueued bucket
+        self.muted = False                    # True: this backward pass is local (gradient accumulation), nothing is announced or enqueued
+        self.pre_reduce = None                # callback(lo, hi) in front of every collective, on the stream that enqueues it
 
     def _stream_wait(self, waiter, waited):
+        if self.muted:
+            return
         self._tick += 1
         self._waits[(waiter, waited)] = self._tick
 
@@ -113,11 +122,15 @@ class OverlappedGradAllReduce:
             self._check_ordered(lo, hi, cur)
             if self.log is not None:
                 self.log.append((lo, hi, cur, [p for p in self._pieces if p[0] < hi and p[1] > lo]))
+            if self.pre_reduce is not None:
+                self.pre_reduce(lo, hi)
             op = dist.ReduceOp.AVG if self._avg else dist.ReduceOp.SUM
             self._handles.append(dist.all_reduce(self.arena[lo:hi], op=op, group=self.group, async_op=True))
 
     def _ready(self, lo: int, hi: int):
         # layers complete in arena order, so [0, hi) is final; the caller is on the stream that produced [lo, hi)
+        if self.muted:
+            return
         self._tick += 1
         self._pieces.append((lo, hi, self._stream_id(), self._tick))
         self._final = max(self._final, hi)
@@ -128,6 +141,8 @@ class OverlappedGradAllReduce:
     def _backward_done(self):
         # remaining weights + the whole bias region (bias gradients are accumulated by every layer's kernel, on either stream: the
         # plan calls this after its main stream has waited for the side stream, which _check_ordered verifies for the weight ranges)
+        if self.muted:
+            return
         self._reduce(self._sent, self.arena.numel())
         self._sent = self.arena.numel()
 
@@ -172,8 +187,9 @@ def make_grad_reducer(model: torch.nn.Module, device, group=None):
       hands over after the head) with ``GradAllReduce``;
     * anything else (CPU tensors, custom modules): ``GradAllReduce`` over all parameters.
 
-    The arena path OVERWRITES gradients every backward (no accumulation across backward calls), which is what the
-    reference's loop does (zero_grad before every backward, trainer.py:64)."""
+    The arena path OVERWRITES gradients every backward, which is what the reference's loop does (zero_grad before every backward,
+    trainer.py:64); accumulation over several backward passes is ``yolo.optim.GradAccumulator(model, K, reducer)``, which keeps the sum
+    beside the arena and lets the reducer work on the last pass of a group only."""
     on_gpu = torch.device(device).type == "cuda"
     if on_gpu and hasattr(model, "_fusable") and model._fusable():
         return OverlappedGradAllReduce(model.hip_plan(), device, group=group)

@@ -23,9 +23,13 @@ _PARTS = ("total", "coord", "conf_obj", "conf_noobj", "class")
 _CLIP = 10.0
 
 
-def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, writer=None, scaler=None, ema=None) -> dict[str, float]:
+def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, writer=None, scaler=None, ema=None, accum_steps: int = 1) -> dict[str, float]:
     """One pass over ``dataloader``; returns the mean of each loss component.  ``ema``: a ``yolo.optim.ModelEMA`` of ``model``, moved after every
     optimizer step (on a device it is enqueued like the step itself, nothing waits).
+
+    ``accum_steps`` = K > 1: gradient accumulation (``yolo.optim.GradAccumulator``) -- K batches per optimizer step, EMA update and all-reduce;
+    the effective batch is K times the loader's (times the ranks).  A last group of fewer than K batches is dropped, not applied (the spirit of
+    ``drop_last=True``), and its losses do not enter the returned means.
 
     ``scaler`` (the reference's fp16 autocast + GradScaler branch, trainer.py:69-83) is accepted and not used: on a ROCm
     device the engine already computes in bf16 with fp32 accumulation and fp32 master weights, which needs no loss scaling;
@@ -42,6 +46,8 @@ def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, wri
         if allreduce is None:
             allreduce = make_grad_reducer(model, device)
             model._yolo_grad_reducer = allreduce
+    if accum_steps > 1:
+        return _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, writer, ema, int(accum_steps), allreduce, fused_clip)
     t0 = time.time()
     for batch_idx, (images, targets) in enumerate(dataloader):
         images = images.to(device, non_blocking=True)
@@ -72,6 +78,53 @@ def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, wri
                 for k in _PARTS:
                     writer.add_scalar(f"batch/{k}_loss", parts[k], step)
             t0 = time.time()
+    return {k: v / max(n, 1) for k, v in sums.items()}
+
+
+def _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, writer, ema, K, allreduce, fused_clip) -> dict[str, float]:
+    """train_epoch's loop with K batches per optimizer step.  The accumulator is kept on the model like the reducer it mutes (its buffers are as
+    large as the gradients); it starts every epoch at the head of a group."""
+    from ..optim import GradAccumulator
+    accum = getattr(model, "_yolo_grad_accumulator", None)
+    if accum is None or accum.steps != K or accum.reducer is not allreduce:
+        accum = model._yolo_grad_accumulator = GradAccumulator(model, K, allreduce)
+    accum.micro = 0
+    sums = dict.fromkeys(_PARTS, 0.0)
+    n = 0
+    group = []                      # the loss parts of the open group: they count once its step is applied
+    t0 = time.time()
+    for batch_idx, (images, targets) in enumerate(dataloader):
+        images = images.to(device, non_blocking=True)
+        targets = targets.to(device, non_blocking=True)
+        optimizer.zero_grad(set_to_none=True)        # the accumulator holds the sum (and with an arena the views are re-assigned anyway)
+        accum.before_backward()
+        loss, parts = criterion(model(images), targets)
+        loss.backward()
+        group.append(parts)
+        if accum.after_backward(getattr(parts, "device_flag", None)):
+            if not fused_clip:
+                torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=_CLIP)
+            if hasattr(optimizer, "skip_if"):
+                optimizer.skip_if = accum.skip_if    # one flagged batch cancels the group's step (and, through last_skip, the EMA's)
+            optimizer.step()
+            if ema is not None:
+                ema.update(model)
+            for done in group:
+                for k in _PARTS:
+                    sums[k] += done[k]
+                n += 1
+            group = []
+        if (batch_idx + 1) % 10 == 0:
+            print(f"Epoch [{epoch}] Batch [{batch_idx + 1}/{len(dataloader)}] Loss: {parts['total']:.4f} "
+                  f"(coord: {parts['coord']:.4f}, conf_obj: {parts['conf_obj']:.4f}, conf_noobj: {parts['conf_noobj']:.4f}, "
+                  f"class: {parts['class']:.4f}) Time: {time.time() - t0:.2f}s")
+            if writer is not None:
+                step = (epoch - 1) * len(dataloader) + batch_idx
+                for k in _PARTS:
+                    writer.add_scalar(f"batch/{k}_loss", parts[k], step)
+            t0 = time.time()
+    for r in getattr(accum, "_overlapped", ()):
+        r.muted = False              # a dropped incomplete group leaves the reducer as it was found
     return {k: v / max(n, 1) for k, v in sums.items()}
 
 
@@ -113,7 +166,7 @@ def seed_epoch(seed: int, epoch: int, train_loader=None) -> None:
 def train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, num_epochs: int, checkpoint_dir,
           save_frequency: int = 5, writer=None, compute_map: bool = False, map_frequency: int = 5, num_classes: int = 20,
           start_epoch: int = 1, best_val_loss_init: float = None, best_map_init: float = None, scaler=None,
-          seed: int | None = None, record: dict | None = None, ema=None) -> dict[str, float]:
+          seed: int | None = None, record: dict | None = None, ema=None, accum_steps: int = 1) -> dict[str, float]:
     """Epoch loop with the reference's checkpoint policy: latest every epoch, every ``save_frequency``
     epochs, best validation loss, best mAP50:95.
 
@@ -123,7 +176,9 @@ def train(model, train_loader, val_loader, criterion, optimizer, scheduler, devi
 
     ``ema``: a ``yolo.optim.ModelEMA`` of ``model``: updated after every step, and the copy that is validated -- best-loss and best-mAP selection
     follow the averaged weights.  Every checkpoint then carries them next to the raw ones (checkpoints.py).  With several ranks each keeps its own
-    average; they are identical because the parameters are, and nothing is communicated."""
+    average; they are identical because the parameters are, and nothing is communicated.
+
+    ``accum_steps``: batches per optimizer step (``train_epoch``)."""
     best_val = float("inf") if best_val_loss_init is None else best_val_loss_init
     best_map = 0.0 if best_map_init is None else best_map_init
     final_train = None
@@ -131,7 +186,7 @@ def train(model, train_loader, val_loader, criterion, optimizer, scheduler, devi
         print(f"\n===== Epoch {epoch}/{num_epochs} =====")
         if seed is not None:
             seed_epoch(seed, epoch, train_loader)
-        tr = train_epoch(model, train_loader, criterion, optimizer, device, epoch, writer, scaler, ema=ema)
+        tr = train_epoch(model, train_loader, criterion, optimizer, device, epoch, writer, scaler, ema=ema, accum_steps=accum_steps)
         print("  train:", {k: round(v, 4) for k, v in tr.items()})
         want_map = compute_map and (epoch % map_frequency == 0 or epoch == num_epochs)
         va = validate(model if ema is None else ema.module, val_loader, criterion, device, compute_map=want_map, num_classes=num_classes)
