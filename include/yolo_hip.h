@@ -631,30 +631,41 @@ int yolo_preprocess_u8(const unsigned char *src_u8, int N, int Hs, int Ws, int H
  * the file and draws the random parameters; crop -> Resize (Pillow BILINEAR, bit-exact) -> ColorJitter operations in the
  * sampled order (Pillow's ImageEnhance.Brightness / ImageEnhance.Color and an H-byte shift through its HSV conversion,
  * bit-exact) -> ToTensor -> Normalize run here for a whole batch of images of DIFFERENT sizes.
+ * The Darknet recipe (yolo.dataset._DarknetAugment) goes the same way: a window that may leave the image (YOLO_AUG_F_EDGE:
+ * row and column are clamped to the image, i.e. the border pixels are replicated), a mirror of the output columns
+ * (YOLO_AUG_F_FLIP) and YOLO_AUG_HSV, one round trip through Pillow's 8-bit HSV with the H byte shifted and the S and V
+ * bytes scaled.
  * One descriptor per image; the images lie packed in one uint8 buffer (HWC RGB). */
 typedef struct yolo_augment_desc {
     int64_t src_off;            /* byte offset of the image in the packed buffer */
     int64_t tmp_off;            /* byte offset of its [ch][Wo][3] slice in tmp_u8 (used when cw != Wo) */
     int32_t Hs, Ws;             /* decoded size */
-    int32_t top, left, ch, cw;  /* crop (the whole image for validation) */
+    int32_t top, left, ch, cw;  /* crop (the whole image for validation); with YOLO_AUG_F_EDGE a window that may leave the image */
     /* Pillow's tables for cw -> Wo and ch -> Ho in DEVICE memory: int32 [out][2 + k] rows of (first input index, count,
        k 22-bit fixed-point weights); NULL / k = 0 for an axis whose size does not change */
     const int32_t *htab;
     const int32_t *vtab;
     int32_t hk, vk;
     int32_t n_ops;              /* 0..3 colour operations, applied in the order of ops[] */
-    int32_t ops[3];             /* YOLO_AUG_BRIGHTNESS / _SATURATION / _HUE */
-    float brightness;           /* ImageEnhance.Brightness factor */
-    float saturation;           /* ImageEnhance.Color factor */
+    int32_t ops[3];             /* YOLO_AUG_BRIGHTNESS / _SATURATION / _HUE, or YOLO_AUG_HSV alone */
+    float brightness;           /* ImageEnhance.Brightness factor; YOLO_AUG_HSV: the factor of the V byte */
+    float saturation;           /* ImageEnhance.Color factor; YOLO_AUG_HSV: the factor of the S byte */
     int32_t hue_shift;          /* int(delta * 255), added to the H byte modulo 256 */
-    int32_t reserved;
+    int32_t flags;              /* YOLO_AUG_F_*; 0: the crop lies inside the image and is not mirrored */
 } yolo_augment_desc;
 #define YOLO_AUG_BRIGHTNESS 0
 #define YOLO_AUG_SATURATION 1
 #define YOLO_AUG_HUE 2
+/* (3 is not assigned) */
+#define YOLO_AUG_HSV 4          /* H := (H + hue_shift) mod 256, S := min(255, trunc(S * saturation)), V := min(255, trunc(V * brightness)),
+                                   fp32 products; shares the factor fields, so it is the only entry of ops[]; factors finite and >= 0 */
+#define YOLO_AUG_F_FLIP 1       /* mirror the output columns (after the resize, before the colour operations) */
+#define YOLO_AUG_F_EDGE 2       /* the window may leave the image: reads are clamped to the image (edge replication); it must still
+                                   intersect the image, and |top|, |left|, ch, cw <= 32768 */
 
-/* descs_host is validated before any HIP call (crop inside its image and inside src_bytes, tables present where a size
- * changes, tmp slice inside tmp_bytes, n_ops <= 3, known operations); descs_dev is the same array in device memory, which
+/* descs_host is validated before any HIP call (known flags, crop inside its image -- with YOLO_AUG_F_EDGE: intersecting it -- and
+ * the image inside src_bytes, tables present where a size changes, tmp slice inside tmp_bytes, n_ops <= 3, known operations,
+ * YOLO_AUG_HSV alone and with finite factors >= 0); descs_dev is the same array in device memory, which
  * the kernels read.  Two launches for the whole batch: a horizontal pass over the crop rows of every image that needs
  * one into tmp_u8, then a vertical pass that finishes each output pixel in registers.  mean3 / std3 are HOST pointers.
  * Outputs (each may be NULL, not all): out_nhwc4 = zero-haloed NHWC4 bf16 [N][Ho+2h][Wo+2h][4] (interior written, channel

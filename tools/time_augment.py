@@ -1,8 +1,10 @@
 #!/usr/bin/env python3
 """micro-benchmark: images/s of yolo_augment_u8 for a batch of 64 VOC-sized images (sampled crops, all three colour operations) into the stem's
 NHWC4 buffer, next to images/s of the host path (_Augment.apply + ToTensor + Normalize on Pillow) on the same images with 1 and 16 worker
-processes.  Warm-up, then REPS timed runs of each; median and spread (min .. max) are printed."""
-import os, statistics, sys, time
+processes.  Warm-up, then REPS timed runs of each; median and spread (min .. max) are printed.
+--recipe darknet: the same images with parameters from _DarknetAugment.sample (windows past the image border, flips, the HSV operation).
+--device-only: skip the host path."""
+import argparse, os, statistics, sys, time
 from multiprocessing import Pool
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "yolo-v1_amd"))
@@ -10,25 +12,25 @@ import numpy as np
 import torch
 from PIL import Image
 from yolo.augment import collate_u8
-from yolo.dataset import _Augment
+from yolo.dataset import RECIPES
 from yolo.inference import _Preprocess
 
 N, REPS = 64, 7
 SIZES = [(375, 500), (500, 375), (333, 500), (500, 333), (281, 500), (374, 500), (500, 400), (442, 500)]      # (H, W) common in PASCAL VOC
 
 
-def make():
+def make(recipe):
     torch.manual_seed(0)
     rng = np.random.default_rng(0)
-    aug = _Augment((448, 448))
+    aug = RECIPES[recipe]((448, 448))
     images = [rng.integers(0, 256, size=SIZES[i % len(SIZES)] + (3,), dtype=np.uint8) for i in range(N)]
     return images, [aug.sample(im.shape[1], im.shape[0]) for im in images]
 
 
 def host_one(job):
-    im, p = job
+    im, p, recipe = job
     torch.set_num_threads(1)
-    return _Preprocess()(_Augment((448, 448)).apply(Image.fromarray(im), [], p)[0]).shape[0]
+    return _Preprocess()(RECIPES[recipe]((448, 448)).apply(Image.fromarray(im), [], p)[0]).shape[0]
 
 
 def spread(rates):
@@ -36,9 +38,14 @@ def spread(rates):
 
 
 if __name__ == "__main__":
-    images, params = make()
-    jobs = list(zip(images, params))
-    for workers in (1, 16):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--recipe", choices=sorted(RECIPES), default="reference")
+    ap.add_argument("--device-only", action="store_true")
+    a = ap.parse_args()
+    images, params = make(a.recipe)
+    jobs = [(im, p, a.recipe) for im, p in zip(images, params)]
+    print(f"recipe {a.recipe}")
+    for workers in (() if a.device_only else (1, 16)):
         with Pool(workers) as pool:
             pool.map(host_one, jobs)          # warm-up: imports, Pillow's tables
             rates = []
@@ -46,11 +53,11 @@ if __name__ == "__main__":
                 t0 = time.perf_counter()
                 pool.map(host_one, jobs * 2, chunksize=max(1, 2 * N // (4 * workers)))
                 rates.append(2 * N / (time.perf_counter() - t0))
-        print(f"host _Augment + _finish, {workers:2d} worker process(es): {spread(rates)}")
+        print(f"host {RECIPES[a.recipe].__name__} + _finish, {workers:2d} worker process(es): {spread(rates)}")
     if not torch.cuda.is_available():
         sys.exit("no GPU: the device path is not measured")
     from yolo.engine import Act
-    batch = collate_u8([(torch.from_numpy(im), p, torch.zeros(1)) for im, p in jobs], pin_memory=True)[0]
+    batch = collate_u8([(torch.from_numpy(im), p, torch.zeros(1)) for im, p, _ in jobs], pin_memory=True)[0]
     dev = batch.to("cuda")
     act = Act(N, 448, 448, 4, 3, dev.device)
     for _ in range(5):

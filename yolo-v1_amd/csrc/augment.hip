@@ -2,6 +2,9 @@
 // per-image crop -> Resize (Pillow BILINEAR, bit-exact) -> ColorJitter operations in the sampled order (Pillow's
 // ImageEnhance.Brightness / .Color and the HSV hue shift, bit-exact: augment_math.h) -> ToTensor -> Normalize -> the stem's
 // input format (zero-haloed NHWC4 bf16), NCHW fp32 and / or the augmented uint8 image.
+// The Darknet recipe uses the descriptor's flags: YOLO_AUG_F_EDGE, a window that may leave the image (row and column clamped
+// to it), YOLO_AUG_F_FLIP, mirrored output columns (the vertical pass reads the mirrored column of stage 1), and the
+// YOLO_AUG_HSV operation.  flags == 0 takes the unclamped loops, as before the flags existed.
 // Replaces the per-sample host transforms of the reference (src/yolo/dataset.py:288-319 RandomResizedCrop + ColorJitter,
 // 325-409 the transform calls of __getitem__), which run one PIL image at a time on the host and ship 2.4 MB of fp32 per
 // image; here the host decodes the file and draws the random parameters (yolo/augment.py, yolo/dataset.py).
@@ -11,6 +14,7 @@
 // image, so the descriptor reads are wave-uniform.  Integer arithmetic for the resize; the colour operations and the
 // normalisation are correctly rounded IEEE operations without contraction (this file is built with -ffp-contract=off and
 // uses the _rn intrinsics).  Byte work bound by memory latency: one thread per output pixel (3 channels).
+#include <float.h>
 #include "common.h"
 #include "augment_math.h"
 
@@ -37,13 +41,25 @@ __global__ void __launch_bounds__(256) augment_h_u8_kernel(const unsigned char *
     const int *row = d.htab + (long)xx * (2 + hk);
     const int x0 = row[0], cnt = row[1];
     const int *k = row + 2;
-    const unsigned char *s = src + d.src_off + ((long)(d.top + y) * d.Ws + d.left + x0) * 3;
+    const int flags = d.flags;                                  // wave-uniform: blockIdx.y is the image
     int a0 = 1 << (AUG_BITS - 1), a1 = a0, a2 = a0;
-    for (int x = 0; x < cnt; ++x) {
-        const int w = k[x];
-        a0 += (int)s[3 * x] * w;
-        a1 += (int)s[3 * x + 1] * w;
-        a2 += (int)s[3 * x + 2] * w;
+    if (flags & YOLO_AUG_F_EDGE) {
+        const unsigned char *s = src + d.src_off + (long)yolo_aug::src_row(d.top, y, d.Hs, flags) * d.Ws * 3;
+        for (int x = 0; x < cnt; ++x) {
+            const int w = k[x];
+            const unsigned char *px = s + yolo_aug::src_col(d.left, x0 + x, d.Ws, flags) * 3;
+            a0 += (int)px[0] * w;
+            a1 += (int)px[1] * w;
+            a2 += (int)px[2] * w;
+        }
+    } else {
+        const unsigned char *s = src + d.src_off + ((long)(d.top + y) * d.Ws + d.left + x0) * 3;
+        for (int x = 0; x < cnt; ++x) {
+            const int w = k[x];
+            a0 += (int)s[3 * x] * w;
+            a1 += (int)s[3 * x + 1] * w;
+            a2 += (int)s[3 * x + 2] * w;
+        }
     }
     unsigned char *o = tmp + d.tmp_off + (long)idx * 3;
     o[0] = (unsigned char)aug_clip8(a0); o[1] = (unsigned char)aug_clip8(a1); o[2] = (unsigned char)aug_clip8(a2);
@@ -60,19 +76,40 @@ __global__ void __launch_bounds__(256) augment_v_color_norm_kernel(const unsigne
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= Ho * Wo) return;
     const int xx = idx % Wo, yy = idx / Wo;
+    const int flags = d.flags;                                  // wave-uniform: blockIdx.y is the image
+    const int sx = yolo_aug::stage1_col(xx, Wo, flags);         // the output position stays (yy, xx)
     // stage 1 of this image: its slice of tmp (rows of Wo pixels), or the crop inside the source (rows of Ws pixels)
     const unsigned char *in;
     long row_bytes;
     if (d.hk > 0) {
-        in = tmp + d.tmp_off + (long)xx * 3;
+        in = tmp + d.tmp_off + (long)sx * 3;
         row_bytes = (long)Wo * 3;
     } else {
-        in = src + d.src_off + ((long)d.top * d.Ws + d.left + xx) * 3;
+        in = src + d.src_off + ((long)d.top * d.Ws + d.left + sx) * 3;
         row_bytes = (long)d.Ws * 3;
     }
     int r, g, b;
     const int vk = d.vk;
-    if (vk > 0) {
+    if ((flags & YOLO_AUG_F_EDGE) && d.hk == 0) {
+        // the window may leave the image and stage 1 is the source itself: every row and the column are clamped to it
+        const unsigned char *col = src + d.src_off + (long)yolo_aug::src_col(d.left, sx, d.Ws, flags) * 3;
+        row_bytes = (long)d.Ws * 3;
+        if (vk > 0) {
+            const int *row = d.vtab + (long)yy * (2 + vk);
+            const int y0 = row[0], cnt = row[1];
+            const int *k = row + 2;
+            int a0 = 1 << (AUG_BITS - 1), a1 = a0, a2 = a0;
+            for (int y = 0; y < cnt; ++y) {
+                const int w = k[y];
+                const unsigned char *s = col + (long)yolo_aug::src_row(d.top, y0 + y, d.Hs, flags) * row_bytes;
+                a0 += (int)s[0] * w; a1 += (int)s[1] * w; a2 += (int)s[2] * w;
+            }
+            r = aug_clip8(a0); g = aug_clip8(a1); b = aug_clip8(a2);
+        } else {
+            const unsigned char *s = col + (long)yolo_aug::src_row(d.top, yy, d.Hs, flags) * row_bytes;
+            r = s[0]; g = s[1]; b = s[2];
+        }
+    } else if (vk > 0) {
         const int *row = d.vtab + (long)yy * (2 + vk);
         const int y0 = row[0], cnt = row[1];
         const int *k = row + 2;
@@ -131,7 +168,14 @@ YOLO_API int yolo_augment_u8(const unsigned char *src, int64_t src_bytes, const 
         if (d.Hs <= 0 || d.Ws <= 0 || d.Hs > 32768 || d.Ws > 32768 || d.src_off < 0 || d.src_off + (int64_t)d.Hs * d.Ws * 3 > src_bytes)
             return fail(YOLO_E_ARG, "yolo_augment_u8: image %d (%d x %d at byte %lld) lies outside the %lld-byte buffer", n, d.Hs, d.Ws, (long long)d.src_off,
                         (long long)src_bytes);
-        if (d.top < 0 || d.left < 0 || d.ch <= 0 || d.cw <= 0 || d.top > d.Hs - d.ch || d.left > d.Ws - d.cw)
+        if (d.flags & ~(YOLO_AUG_F_FLIP | YOLO_AUG_F_EDGE)) return fail(YOLO_E_ARG, "yolo_augment_u8: image %d: unknown flag bits 0x%x", n, (unsigned)d.flags);
+        if (d.flags & YOLO_AUG_F_EDGE) {
+            if (d.ch <= 0 || d.cw <= 0 || d.ch > 32768 || d.cw > 32768 || d.top < -32768 || d.top > 32768 || d.left < -32768 || d.left > 32768)
+                return fail(YOLO_E_ARG, "yolo_augment_u8: image %d: window (top %d, left %d, %d x %d) out of range", n, d.top, d.left, d.ch, d.cw);
+            if (d.top >= d.Hs || d.top + d.ch <= 0 || d.left >= d.Ws || d.left + d.cw <= 0)
+                return fail(YOLO_E_ARG, "yolo_augment_u8: image %d: window (top %d, left %d, %d x %d) misses its %d x %d image", n, d.top, d.left, d.ch, d.cw, d.Hs,
+                            d.Ws);
+        } else if (d.top < 0 || d.left < 0 || d.ch <= 0 || d.cw <= 0 || d.top > d.Hs - d.ch || d.left > d.Ws - d.cw)
             return fail(YOLO_E_ARG, "yolo_augment_u8: image %d: crop (top %d, left %d, %d x %d) outside its %d x %d image", n, d.top, d.left, d.ch, d.cw, d.Hs, d.Ws);
         if (d.cw != Wo) {
             if (!d.htab || d.hk <= 0) return fail(YOLO_E_ARG, "yolo_augment_u8: image %d: width %d -> %d needs the horizontal table", n, d.cw, Wo);
@@ -143,8 +187,16 @@ YOLO_API int yolo_augment_u8(const unsigned char *src, int64_t src_bytes, const 
         }
         if (d.ch != Ho ? (!d.vtab || d.vk <= 0) : d.vk != 0) return fail(YOLO_E_ARG, "yolo_augment_u8: image %d: height %d -> %d and the vertical table disagree", n, d.ch, Ho);
         if (d.n_ops < 0 || d.n_ops > 3) return fail(YOLO_E_ARG, "yolo_augment_u8: image %d: %d colour operations (0..3)", n, d.n_ops);
-        for (int i = 0; i < d.n_ops; ++i)
-            if (d.ops[i] < YOLO_AUG_BRIGHTNESS || d.ops[i] > YOLO_AUG_HUE) return fail(YOLO_E_ARG, "yolo_augment_u8: image %d: unknown colour operation %d", n, d.ops[i]);
+        for (int i = 0; i < d.n_ops; ++i) {
+            if (d.ops[i] == YOLO_AUG_HSV) {
+                if (d.n_ops != 1) return fail(YOLO_E_ARG, "yolo_augment_u8: image %d: YOLO_AUG_HSV shares the factor fields and has to be the only operation", n);
+                if (!(d.saturation >= 0.0f && d.saturation <= FLT_MAX && d.brightness >= 0.0f && d.brightness <= FLT_MAX))
+                    return fail(YOLO_E_ARG, "yolo_augment_u8: image %d: YOLO_AUG_HSV factors (S %g, V %g) must be finite and >= 0", n, (double)d.saturation,
+                                (double)d.brightness);
+            } else if (d.ops[i] < YOLO_AUG_BRIGHTNESS || d.ops[i] > YOLO_AUG_HUE) {
+                return fail(YOLO_E_ARG, "yolo_augment_u8: image %d: unknown colour operation %d", n, d.ops[i]);
+            }
+        }
     }
     hipStream_t s = STRM(stream);
     if (max_rows > 0) {

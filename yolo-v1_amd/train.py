@@ -63,6 +63,10 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0, help="train on N synthetic images (no dataset needed)")
     ap.add_argument("--device-augment", action="store_true",
                     help="VOC only: loaders ship decoded uint8 images + sampled parameters, crop / resize / colour jitter / normalise run on the device")
+    ap.add_argument("--augment", choices=["reference", "darknet"], default="reference",
+                    help="VOC only, the training augmentation: reference = RandomResizedCrop + ColorJitter; darknet = the YOLOv1 paper's recipe (scaling "
+                         "and translation by up to 20 %% past the image border, horizontal flip, exposure and saturation up to x1.5 and hue +-0.1 in "
+                         "HSV); with and without --device-augment")
     ap.add_argument("--voc-root", default=None, help="dataset root (default: $VOC_ROOT or ./data)")
     ap.add_argument("--deterministic", action="store_true",
                     help="EngineConfig.DETERMINISTIC: every order-dependent sum of the training step runs order-fixed (bit-reproducible steps and --resume)")
@@ -77,6 +81,8 @@ def main():
     a = ap.parse_args()
     if a.accum_steps < 1:
         ap.error("--accum-steps must be at least 1")
+    if a.augment != "reference" and a.synthetic:
+        ap.error("--augment needs the VOC datasets (synthetic samples are not augmented)")
     if a.deterministic:
         if a.backbone == "resnet50":
             # (the training loop puts the whole model in train(): there is no eval-mode trunk to ask for here)
@@ -107,7 +113,7 @@ def main():
         train_ds, val_ds = SyntheticYOLODataset(a.synthetic, seed=0), SyntheticYOLODataset(max(a.batch_size, a.synthetic // 8), seed=1)
     else:
         train_ds = create_voc_datasets([("2007", "trainval"), ("2012", "train")], augment=True, root=a.voc_root,
-                                       device_transform=a.device_augment)     # the reference's splits (src/train.py:106-122)
+                                       device_transform=a.device_augment, recipe=a.augment)     # the reference's splits (src/train.py:106-122)
         val_ds = create_voc_datasets([("2012", "val")], augment=False, root=a.voc_root, device_transform=a.device_augment)
     collate = None
     if a.device_augment:
@@ -171,6 +177,8 @@ def main():
     if a.accum_steps > 1:          # (1: the call, and the checkpoint's keys, are those of a run without the option)
         record = {**(record or {}), "accum_steps": a.accum_steps}
         extra["accum_steps"] = a.accum_steps
+    if a.augment != "reference":          # (the default: the checkpoint's keys are those of a run without the option)
+        record = {**(record or {}), "augment": a.augment}
     res = training.train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, a.epochs, ckdir,
                          save_frequency=a.save_frequency, compute_map=a.compute_map, start_epoch=start_epoch,
                          best_val_loss_init=best_val, best_map_init=best_map, seed=a.seed, record=record, ema=ema, **extra)

@@ -116,10 +116,11 @@ class AugmentDesc(ctypes.Structure):
                 ("htab", c_void_p), ("vtab", c_void_p),
                 ("hk", ctypes.c_int32), ("vk", ctypes.c_int32),
                 ("n_ops", ctypes.c_int32), ("ops", ctypes.c_int32 * 3),
-                ("brightness", ctypes.c_float), ("saturation", ctypes.c_float), ("hue_shift", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+                ("brightness", ctypes.c_float), ("saturation", ctypes.c_float), ("hue_shift", ctypes.c_int32), ("flags", ctypes.c_int32)]
 
 
-AUG_BRIGHTNESS, AUG_SATURATION, AUG_HUE = 0, 1, 2      # YOLO_AUG_* (include/yolo_hip.h)
+AUG_BRIGHTNESS, AUG_SATURATION, AUG_HUE, AUG_HSV = 0, 1, 2, 4      # YOLO_AUG_* (include/yolo_hip.h); 3 is not assigned
+AUG_F_FLIP, AUG_F_EDGE = 1, 2                                       # YOLO_AUG_F_*
 EPI_NONE, EPI_BIAS, EPI_BIAS_LRELU, EPI_MUL_DLRELU, EPI_BIAS_ADD_LRELU = 0, 1, 2, 3, 4
 NMS_INFERENCE, NMS_METRICS = 0, 1
 

@@ -6,7 +6,9 @@ file and draws the random parameters (``yolo.dataset._Augment.sample``); a batch
 different sizes plus one descriptor per image (``U8Batch``), and two kernel launches do crop -> Pillow-exact resize -> colour
 operations in the sampled order -> ToTensor -> Normalize, into the stem's NHWC4 bf16 buffer (``Plan.forward``) or an NCHW fp32
 tensor (``U8Batch.to_tensor``).  The result is bit-identical to the host path (``_Augment.apply`` + ``_Preprocess``) for the
-same parameters: tests/test_gpu_augment.py.
+same parameters: tests/test_gpu_augment.py.  The Darknet recipe (``_DarknetAugment``: ``JitterParams`` entries) goes through the same two
+launches -- window with edge replication, flip, one HSV operation -- and may share a batch with ``AugParams`` entries:
+tests/test_gpu_darknet_augment.py.
 
     ds = create_voc_datasets(..., device_transform=True)
     loader = DataLoader(ds, batch_size=64, collate_fn=collate_u8, pin_memory=True)
@@ -17,6 +19,7 @@ same parameters: tests/test_gpu_augment.py.
 from __future__ import annotations
 
 import ctypes
+import math
 from typing import Sequence
 
 import numpy as np
@@ -24,7 +27,7 @@ import torch
 from PIL import Image
 
 from . import _hip
-from .dataset import AugParams, _Augment
+from .dataset import AugParams, JitterParams, _Augment, _DarknetAugment
 from .preprocess import MEAN, STD, bilinear_tables
 
 # (in_size, out_size, device index) -> (int32 device tensor [out][2 + k]: first input index, count, k weights; k).  Never evicted:
@@ -43,24 +46,31 @@ def _device_table(in_size: int, out_size: int, dev: torch.device):
 
 class U8Batch:
     """N decoded RGB images of different sizes, packed HWC into one uint8 buffer, with the parameters of their crop and colour
-    operations.  Stands for the (N, 3, H, W) fp32 batch the host path would have produced: ``shape``, ``is_cuda``, ``device``,
+    operations: one ``AugParams`` (reference recipe, crop inside the image) or ``JitterParams`` (Darknet recipe, a window that may
+    leave the image) per image, in any mix.  Stands for the (N, 3, H, W) fp32 batch the host path would have produced: ``shape``, ``is_cuda``, ``device``,
     ``to`` and ``pin_memory`` behave as a tensor's do, so loaders and training loops pass it along unchanged."""
 
     requires_grad = False
 
-    def __init__(self, data: torch.Tensor, sizes: Sequence, params: Sequence[AugParams], size=(448, 448), mean=MEAN, std=STD):
+    def __init__(self, data: torch.Tensor, sizes: Sequence, params: Sequence, size=(448, 448), mean=MEAN, std=STD):
         if data.dtype != torch.uint8 or data.dim() != 1:
             raise ValueError("U8Batch expects a flat uint8 buffer")
         if len(sizes) != len(params) or not sizes:
-            raise ValueError("U8Batch needs one (H, W) and one AugParams per image, and at least one image")
+            raise ValueError("U8Batch needs one (H, W) and one AugParams / JitterParams per image, and at least one image")
         self.data, self.sizes, self.params = data, [tuple(int(v) for v in s) for s in sizes], list(params)
         self.size, self.mean, self.std = (int(size[0]), int(size[1])), tuple(mean), tuple(std)
         self.offsets, off = [], 0
         for (h, w), p in zip(self.sizes, self.params):
-            if not (0 <= p.top and 0 <= p.left and p.ch > 0 and p.cw > 0 and p.top + p.ch <= h and p.left + p.cw <= w):
-                raise ValueError(f"crop {tuple(p[:4])} outside its {h} x {w} image")
-            if len(p.ops) > 3:
-                raise ValueError("at most 3 colour operations")
+            if isinstance(p, JitterParams):          # only this recipe's window may leave the image; it still has to meet it
+                if not (p.ch > 0 and p.cw > 0 and p.top < h and p.top + p.ch > 0 and p.left < w and p.left + p.cw > 0):
+                    raise ValueError(f"window {tuple(p[:4])} misses its {h} x {w} image")
+                if not (0.0 <= p.saturation < math.inf and 0.0 <= p.exposure < math.inf):
+                    raise ValueError("saturation and exposure must be finite and >= 0")
+            else:
+                if not (0 <= p.top and 0 <= p.left and p.ch > 0 and p.cw > 0 and p.top + p.ch <= h and p.left + p.cw <= w):
+                    raise ValueError(f"crop {tuple(p[:4])} outside its {h} x {w} image")
+                if len(p.ops) > 3:
+                    raise ValueError("at most 3 colour operations")
             self.offsets.append(off)
             off += h * w * 3
         if off != data.numel():
@@ -135,6 +145,12 @@ class U8Batch:
                 if p.ch != Ho:
                     t, d.vk = _device_table(p.ch, Ho, dev)
                     d.vtab = t.data_ptr()
+                if isinstance(p, JitterParams):
+                    inside = 0 <= p.top and 0 <= p.left and p.top + p.ch <= h and p.left + p.cw <= w
+                    d.flags = (_hip.AUG_F_FLIP if p.flip else 0) | (0 if inside else _hip.AUG_F_EDGE)
+                    d.n_ops, d.ops[0] = 1, _hip.AUG_HSV
+                    d.brightness, d.saturation, d.hue_shift = p.exposure, p.saturation, int(p.hue * 255)
+                    continue
                 d.n_ops = len(p.ops)
                 for i, op in enumerate(p.ops):
                     d.ops[i] = op
@@ -170,7 +186,7 @@ class U8Batch:
 
     def to_tensor(self) -> torch.Tensor:
         """the (N, 3, H, W) fp32 batch this object stands for: on the device through yolo_augment_u8, on the CPU through the host
-        path (``_Augment.apply`` on PIL + ToTensor + Normalize) -- the same bits either way"""
+        path (``_Augment.apply`` / ``_DarknetAugment.apply`` on PIL + ToTensor + Normalize) -- the same bits either way"""
         if self.is_cuda:
             out = torch.empty(tuple(self.shape), dtype=torch.float32, device=self.device)
             self._run(nchw=out)
@@ -180,12 +196,12 @@ class U8Batch:
         return torch.stack([finish(im) for im in self._host_images()])
 
     def _host_images(self):
-        aug = _Augment(self.size)
-        return [aug.apply(Image.fromarray(self.image(i).numpy()), [], p)[0] for i, p in enumerate(self.params)]
+        ref, dark = _Augment(self.size), _DarknetAugment(self.size)
+        return [(dark if isinstance(p, JitterParams) else ref).apply(Image.fromarray(self.image(i).numpy()), [], p)[0] for i, p in enumerate(self.params)]
 
 
 def collate_u8(samples, size=(448, 448), pin_memory: bool = False):
-    """collate function for datasets in ``device_transform`` mode: [(uint8 HWC tensor, AugParams, target), ...] ->
+    """collate function for datasets in ``device_transform`` mode: [(uint8 HWC tensor, AugParams or JitterParams, target), ...] ->
     (U8Batch, stacked targets).  ``pin_memory``: pack straight into page-locked memory (a DataLoader with ``pin_memory=True`` pins
     the batch by itself through ``U8Batch.pin_memory``)."""
     images = [s[0] for s in samples]

@@ -12,6 +12,9 @@ to ``torchvision.datasets.VOCDetection`` and ``torchvision.transforms.v2`` (un-v
   * training augmentation = box-aware RandomResizedCrop(scale (0.8, 1.2), ratio (0.8, 1.2)) + ColorJitter(brightness 0.5,
     saturation 0.5, hue 0.1) (dataset.py:288-319), same distributions, drawn from ``torch``'s global RNG -- the random
     STREAM differs from torchvision's, so augmented samples are "parity unpinned" (statistics, not bits);
+  * ``recipe="darknet"`` (additive): the YOLOv1 paper's augmentation instead -- scaling and translation by up to 20 % of the
+    image size past the image border (edge replication), a horizontal flip, exposure and saturation scaled by up to 1.5 and
+    the hue shifted by up to 0.1 in HSV (``_DarknetAugment``);
   * ``download=True`` (kagglehub) is not available offline and raises.
 
 ``encode_target`` restates ``_encode_target`` (dataset.py:487-532); ``SyntheticYOLODataset`` feeds benchmarks and tests.
@@ -89,7 +92,7 @@ def parse_voc_xml(node: ET.Element) -> dict:
     return {node.tag: inner}
 
 
-OP_BRIGHTNESS, OP_SATURATION, OP_HUE = 0, 1, 2      # = YOLO_AUG_* of include/yolo_hip.h
+OP_BRIGHTNESS, OP_SATURATION, OP_HUE, OP_HSV = 0, 1, 2, 4      # = YOLO_AUG_* of include/yolo_hip.h (3 is not assigned)
 
 
 class AugParams(NamedTuple):
@@ -115,6 +118,39 @@ def crop_boxes(boxes, p: AugParams, size) -> List[List[float]]:
         y0, y1 = min(max(y0 - p.top, 0.0), p.ch) * sy, min(max(y1 - p.top, 0.0), p.ch) * sy
         out.append([x0, y0, x1, y1])
     return out
+
+
+class JitterParams(NamedTuple):
+    """What ``_DarknetAugment.sample`` draws for one image: the window (it may extend past any border of the image), the flip, the hue
+    shift (fraction of the hue circle; the H byte moves by ``int(hue * 255)``) and the factors of the S and V bytes.  The host path
+    (``_DarknetAugment.apply``) and the device path (yolo/augment.py -> yolo_augment_u8) both take it."""
+    top: int
+    left: int
+    ch: int
+    cw: int
+    flip: bool = False
+    hue: float = 0.0
+    saturation: float = 1.0
+    exposure: float = 1.0
+
+
+def jitter_boxes(boxes, p: JitterParams, size) -> Tuple[List[List[float]], List[int]]:
+    """pixel-space XYXY boxes shifted into the window, scaled with it to ``size`` = (H, W), clamped to the output and mirrored with
+    it; a box whose clamped width is below 1e-3 W or whose clamped height is below 1e-3 H is dropped (Darknet's rule).  Returns the
+    boxes that stay and their indices in ``boxes``."""
+    H, W = size
+    sx, sy = W / p.cw, H / p.ch
+    out, kept = [], []
+    for i, (x0, y0, x1, y1) in enumerate(boxes):
+        x0, x1 = min(max((x0 - p.left) * sx, 0.0), W), min(max((x1 - p.left) * sx, 0.0), W)
+        y0, y1 = min(max((y0 - p.top) * sy, 0.0), H), min(max((y1 - p.top) * sy, 0.0), H)
+        if p.flip:
+            x0, x1 = W - x1, W - x0
+        if x1 - x0 < 1e-3 * W or y1 - y0 < 1e-3 * H:
+            continue
+        out.append([x0, y0, x1, y1])
+        kept.append(i)
+    return out, kept
 
 
 def _uniform(a: float, b: float) -> float:
@@ -190,6 +226,70 @@ class _Augment:
         return self.apply(image, boxes, self.sample(*image.size))
 
 
+class _DarknetAugment:
+    """The training augmentation of the YOLOv1 paper (section 2.2) and Darknet's yolov1.cfg: a window displaced by up to ``jitter`` of
+    the image size on every side -- it may extend past the image, whose border pixels are then replicated, as Darknet's crop does --
+    resized to ``size``, a horizontal flip with probability ``flip``, and one round trip through HSV with the hue shifted by up to
+    ``hue`` and saturation and exposure (S and V) scaled by up to ``saturation`` / ``exposure`` or their inverses.  H, S and V are
+    Pillow's 8-bit channels (``convert("HSV")``), not Darknet's floats.  Shaped like ``_Augment``: ``sample`` / ``apply``."""
+
+    def __init__(self, size: Tuple[int, int], jitter=0.2, hue=0.1, saturation=1.5, exposure=1.5, flip=0.5):
+        self.size, self.jitter, self.hue, self.saturation, self.exposure, self.flip = size, jitter, hue, saturation, exposure, flip
+
+    @staticmethod
+    def _scale(k: float) -> float:
+        s = _uniform(1.0, k)
+        return 1.0 / s if float(torch.rand(1).item()) < 0.5 else s
+
+    def sample(self, w: int, h: int) -> JitterParams:
+        """Draw the parameters for a w x h image from torch's global generator, in this order: the integers pleft, pright in
+        [-int(w * jitter), int(w * jitter)] (one ``randint`` of two), ptop, pbot in [-int(h * jitter), int(h * jitter)] (likewise), the
+        flip (one ``rand``), the hue (uniform in +-hue), then the saturation and then the exposure, each a uniform s in [1, k]
+        followed by one ``rand`` that inverts it (1 / s) with probability 1/2.  The window is left = pleft, top = ptop,
+        cw = w - pleft - pright, ch = h - ptop - pbot."""
+        dw, dh = int(w * self.jitter), int(h * self.jitter)
+        pleft, pright = torch.randint(-dw, dw + 1, (2,)).tolist()
+        ptop, pbot = torch.randint(-dh, dh + 1, (2,)).tolist()
+        flip = float(torch.rand(1).item()) < self.flip
+        hue = _uniform(-self.hue, self.hue)
+        sat = self._scale(self.saturation)
+        exp = self._scale(self.exposure)
+        return JitterParams(ptop, pleft, h - ptop - pbot, w - pleft - pright, flip, hue, sat, exp)
+
+    @staticmethod
+    def _window(image: Image.Image, p: JitterParams) -> Image.Image:
+        """pixel (y, x) of the window = source pixel (clamp(top + y, 0, h - 1), clamp(left + x, 0, w - 1))"""
+        a = np.asarray(image, dtype=np.uint8)
+        ys = np.clip(np.arange(p.top, p.top + p.ch), 0, a.shape[0] - 1)
+        xs = np.clip(np.arange(p.left, p.left + p.cw), 0, a.shape[1] - 1)
+        return Image.fromarray(np.ascontiguousarray(a[ys][:, xs]))
+
+    @staticmethod
+    def _hsv(img: Image.Image, hue: float, saturation: float, exposure: float) -> Image.Image:
+        hsv = np.array(img.convert("HSV"), dtype=np.uint8)
+        hsv[..., 0] = (hsv[..., 0].astype(np.int16) + int(hue * 255)) % 256
+        for c, f in ((1, saturation), (2, exposure)):
+            hsv[..., c] = np.minimum(np.float32(255), np.trunc(hsv[..., c].astype(np.float32) * np.float32(f))).astype(np.uint8)
+        return Image.fromarray(hsv, "HSV").convert("RGB")
+
+    def geometry(self, image: Image.Image, p: JitterParams) -> Image.Image:
+        """window, PIL bilinear resize, flip"""
+        image = self._window(image, p).resize((self.size[1], self.size[0]), Image.BILINEAR)
+        return image.transpose(Image.FLIP_LEFT_RIGHT) if p.flip else image
+
+    def apply(self, image: Image.Image, boxes: List[List[float]], p: JitterParams):
+        """The host path: window, PIL bilinear resize, flip, the HSV round trip; boxes go with the window and the flip (the ones
+        ``jitter_boxes`` keeps)."""
+        image = self._hsv(self.geometry(image, p), p.hue, p.saturation, p.exposure)
+        return image, jitter_boxes(boxes, p, self.size)[0]
+
+    def __call__(self, image: Image.Image, boxes: List[List[float]]):
+        return self.apply(image, boxes, self.sample(*image.size))
+
+
+RECIPES = {"reference": _Augment, "darknet": _DarknetAugment}
+
+
 class VOCDetectionYOLO(Dataset):
     """PASCAL VOC detection samples as (image tensor (3, H, W), target (S, S, 5B+C)); reference dataset.py:16-588."""
 
@@ -207,9 +307,14 @@ class VOCDetectionYOLO(Dataset):
                           "(VOCdevkit/VOC<year>/...) and pass download=False")
 
     def __init__(self, root: str | Path = None, year: str = "2007", image_set: str = "train", download: bool = False, S: int = 7, B: int = 2,
-                 transform=None, target_size: Tuple[int, int] = (448, 448), augment: bool = True, device_transform: bool = False):
+                 transform=None, target_size: Tuple[int, int] = (448, 448), augment: bool = True, device_transform: bool = False,
+                 recipe: str = "reference"):
         self.S, self.B = S, B
-        # device_transform: __getitem__ returns (decoded uint8 HWC tensor, AugParams, target) for yolo.augment.collate_u8 -- the crop,
+        # recipe: the training augmentation -- "reference" (_Augment, the reference's) or "darknet" (_DarknetAugment, the paper's)
+        if recipe not in RECIPES:
+            raise ValueError(f"recipe must be one of {sorted(RECIPES)}, not {recipe!r}")
+        self.recipe = recipe
+        # device_transform: __getitem__ returns (decoded uint8 HWC tensor, AugParams or JitterParams, target) for yolo.augment.collate_u8 -- the crop,
         # resize, colour jitter and normalisation then run on the device (yolo_augment_u8) with the very parameters drawn here
         if device_transform and transform is not None:
             raise ValueError("device_transform=True cannot run a custom `transform` on the device")
@@ -244,7 +349,7 @@ class VOCDetectionYOLO(Dataset):
         self._finish = _Preprocess(size=target_size)                # ToTensor + Normalize (the resize is a no-op after the crop)
 
     def _get_augmentation_transforms(self):
-        return _Augment(self.target_size)
+        return RECIPES[self.recipe](self.target_size)
 
     def __len__(self) -> int:
         return len(self.ids)
@@ -255,11 +360,16 @@ class VOCDetectionYOLO(Dataset):
         annotation = parse_voc_xml(ET.parse(self.voc_dir / "Annotations" / f"{name}.xml").getroot())
         return image, annotation
 
-    def _augmented_target(self, annotation: dict, w: int, h: int, p: AugParams) -> torch.Tensor:
-        """target of a training sample whose image is cropped by ``p`` (the host and the device path alike)"""
+    def _augmented_target(self, annotation: dict, w: int, h: int, p) -> torch.Tensor:
+        """target of a training sample whose image is cropped by ``p`` (the host and the device path alike); under ``JitterParams`` the
+        boxes that ``jitter_boxes`` drops lose their class ids too"""
         bboxes, class_ids = self._extract_bboxes_from_annotation(annotation)
         pix = [[(x - bw / 2) * w, (y - bh / 2) * h, (x + bw / 2) * w, (y + bh / 2) * h] for x, y, bw, bh in bboxes]
-        pix = crop_boxes(pix, p, self.target_size)
+        if isinstance(p, JitterParams):
+            pix, kept = jitter_boxes(pix, p, self.target_size)
+            class_ids = [class_ids[i] for i in kept]
+        else:
+            pix = crop_boxes(pix, p, self.target_size)
         H, W = self.target_size
         norm = []
         for x0, y0, x1, y1 in pix:
@@ -270,7 +380,7 @@ class VOCDetectionYOLO(Dataset):
     def __getitem__(self, idx: int):
         image, annotation = self._load(idx)
         w, h = image.size
-        augmented = self.augment and isinstance(self.transform, _Augment)
+        augmented = self.augment and isinstance(self.transform, (_Augment, _DarknetAugment))
         if self.device_transform:
             p = self.transform.sample(w, h) if augmented else AugParams(0, 0, h, w)
             target = self._augmented_target(annotation, w, h, p) if augmented else self._parse_voc_annotation(annotation)
@@ -339,12 +449,12 @@ class CombinedVOCDataset(Dataset):
 
 
 def create_voc_datasets(years_and_splits: list, download: bool = True, S: int = 7, B: int = 2, target_size: Tuple[int, int] = (448, 448),
-                        augment: bool = True, root: str | Path = None, device_transform: bool = False) -> Dataset:
+                        augment: bool = True, root: str | Path = None, device_transform: bool = False, recipe: str = "reference") -> Dataset:
     """One VOCDetectionYOLO, or their concatenation, for [(year, image_set), ...] (dataset.py:662-730).  Offline, ``download``
     is honoured only as "the data must already lie under root" (default root: $VOC_ROOT or ./data)."""
     if root is None:
         root = os.environ.get("VOC_ROOT", "data")
     datasets = [VOCDetectionYOLO(root=root, year=y, image_set=s, download=False, S=S, B=B, target_size=target_size, augment=augment,
-                                 device_transform=device_transform)
+                                 device_transform=device_transform, recipe=recipe)
                 for y, s in years_and_splits]
     return datasets[0] if len(datasets) == 1 else CombinedVOCDataset(datasets)
