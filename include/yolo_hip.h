@@ -554,6 +554,41 @@ int yolo_grad_accum(float *dst, const float *x, const float *y, long n, float al
 /* A whole list: one launch per YOLO_MT_MAX tensors, the host table copied into the kernel arguments; empty tensors are legal. */
 int yolo_grad_accum_multi(const yolo_accum_tensor *t, int count, float alpha, const float *skip_flag, yolo_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Classification pretraining of the YOLOv1 trunk (the paper's first stage: 20 convolutions, an average pool and one Linear layer
+ * at 224 x 224).  These three entries EXTEND the reference surface -- mattiaskvist/yolo-v1 has no classifier stage, it downloads
+ * torchvision's ImageNet weights -- so each names the stock-torch operation it replaces instead of a reference line.
+ * Nothing here uses atomics: two calls on the same inputs give the same bits (EngineConfig.DETERMINISTIC needs no second path).
+ * ------------------------------------------------------------------------------------------- */
+
+/* Replaces torch.nn.functional.adaptive_avg_pool2d(x, 1) / x.mean((2, 3)) on the NCHW fp32 features a conv-terminated plan returns.
+ *   x [N][C][HW] fp32 -> y [N][C] fp32, y[n][c] = (sum of the row) * (float)(1.0 / HW)
+ * The sum is formed in fp32 in one fixed order that depends on HW only: a group of L lanes owns a row (L = the smallest power of two
+ * with 4 L >= HW, at most 64; several rows per wave when HW is small), a lane adds its elements j, j + L, .. in that order, the
+ * group folds its L partial sums with an xor butterfly.  Rows need no alignment (HW = 49).
+ * YOLO_E_ARG: a null pointer, N < 0, C < 1, HW < 1.  N = 0 launches nothing. */
+int yolo_gap_fwd(const float *x, int N, int C, int HW, float *y, yolo_stream_t stream);
+/* Its backward (autograd's mean_backward: expand + div): dx[n][c][i] = dy[n][c] * (float)(1.0 / HW), one fp32 multiply per element.
+ * 16-B stores when dx is 16-B aligned, 4-B stores otherwise.  Errors as yolo_gap_fwd. */
+int yolo_gap_bwd(const float *dy, int N, int C, int HW, float *dx, yolo_stream_t stream);
+
+/* Replaces torch.nn.functional.cross_entropy(logits, labels, label_smoothing = e, reduction = "mean"), its autograd backward and
+ * torch.topk(logits, 5) + the membership test of a top-1 / top-5 accuracy, in one pass: one workgroup per row, strided (any K >= 1).
+ *   logits  [N][K] fp32, labels [N] int64
+ *   per row: m = max, s = sum exp(x - m) (fp32 exp, fp64 sum), lse = m + log s;
+ *            loss = (1 - e) (lse - x[label]) + e (lse - mean x)                      (fp64)
+ *   out     [2] fp32: out[0] = the mean of the row losses, added in row order in fp64 by a one-workgroup last stage;
+ *           out[1] = error flag, 1.0 if some label lies outside [0, K).  Such a row contributes zero loss, a zero gradient row and
+ *           no hits, and nothing is read or written out of bounds for it (torch raises / asserts on the device there); the flag is a
+ *           device float an optimizer's skip_flag can take, like out[5] of yolo_loss_fwd_bwd
+ *   dlogits [N][K] fp32 = (softmax - ((1 - e) onehot + e / K)) / N, or NULL (forward only: the same out and hits)
+ *   hits    [N][2] int32: hits[n][0] = top-1, hits[n][1] = top-5.  A hit at k: fewer than k logits of the row are STRICTLY greater than
+ *           the label's -- independent of any sort, and a tie with the label's logit never costs the hit
+ *   work    [N] f64 caller workspace: the row losses
+ * YOLO_E_ARG: a null pointer (dlogits excepted), N < 0, K < 1, label_smoothing outside [0, 1) or NaN.  N = 0: out[0] = NaN, as torch. */
+int yolo_softmax_xent_fwd_bwd(const float *logits, const int64_t *labels, int N, int K, float label_smoothing, float *out,
+                              float *dlogits, int32_t *hits, double *work, yolo_stream_t stream);
+
 /* g *= min(1, max_norm / (sqrt(*norm_sq) + 1e-6))  (stand-alone clip_grad_norm_ for other optimizers). */
 int yolo_clip_scale_f32(float *g, long n, const double *norm_sq, float max_norm, yolo_stream_t stream);
 

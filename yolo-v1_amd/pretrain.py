@@ -1,0 +1,149 @@
+#!/usr/bin/env python3
+"""Classification pretraining of the YOLOv1 trunk -- the stage of the paper (section 2.2) in front of detection training: the first 20
+convolutions, an average pool and one fully connected layer as a 224 x 224 classifier.  The reference has no such stage (it downloads
+torchvision's ImageNet weights for a ResNet-50); this is what gives ``train.py --backbone yolov1`` features to start from.
+
+    python yolo-v1_amd/pretrain.py --device cuda --data-root /data/imagenet --epochs 90 --optimizer sgd --lr 0.1 --label-smoothing 0.1
+    python yolo-v1_amd/pretrain.py --device cuda --synthetic 512 --num-classes 10 --epochs 1
+    python yolo-v1_amd/train.py --device cuda --backbone yolov1 --backbone-weights checkpoints_pretrain/yolo_best_top1.pth ...
+
+``--data-root``: ``<root>/{train,val}/<class>/*`` image folders, the classes being the sorted directory names of ``train``.
+One process, one batch per optimizer step (gradient accumulation and several ranks: see yolo/training/classify.py).
+"""
+
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+from pathlib import Path
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+import torch  # noqa: E402
+from torch.utils.data import DataLoader  # noqa: E402
+
+from yolo import SoftmaxCrossEntropy, YOLOv1Classifier  # noqa: E402
+from yolo.dataset import ImageFolderClassification, SyntheticClassificationDataset  # noqa: E402
+from yolo.training import classify as loop  # noqa: E402
+from yolo.training.trainer import seed_epoch  # noqa: E402
+
+
+def _seed_worker(worker_id: int) -> None:
+    """DataLoader worker: numpy and ``random`` from the seed torch derived for this worker from the loader's generator"""
+    import random
+
+    import numpy as np
+    s = torch.initial_seed() % (1 << 31)
+    np.random.seed(s)
+    random.seed(s)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--device", default="cuda" if torch.cuda.is_available() else "cpu")
+    ap.add_argument("--data-root", default=None, help="<root>/{train,val}/<class>/* image folders")
+    ap.add_argument("--synthetic", type=int, default=0, help="train on N synthetic images of --num-classes classes (no dataset needed)")
+    ap.add_argument("--num-classes", type=int, default=None, help="default: the class directories of --data-root, or 10 with --synthetic")
+    ap.add_argument("--image-size", type=int, default=224)
+    ap.add_argument("--batch-size", type=int, default=64)
+    ap.add_argument("--num-workers", type=int, default=8)
+    ap.add_argument("--epochs", type=int, default=90)
+    ap.add_argument("--optimizer", choices=["adam", "sgd"], default="sgd")
+    ap.add_argument("--lr", type=float, default=1e-2)
+    ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd only")
+    ap.add_argument("--nesterov", action="store_true", help="--optimizer sgd only")
+    ap.add_argument("--weight-decay", type=float, default=5e-4)
+    ap.add_argument("--lr-decay-epochs", default="30,60,80")
+    ap.add_argument("--label-smoothing", type=float, default=0.0)
+    ap.add_argument("--ema-decay", type=float, default=None,
+                    help="keep an exponential moving average of the weights: it is what gets validated, and every checkpoint carries it as "
+                         "ema_state_dict (train.py --backbone-weights .. --use-ema).  Default: no EMA")
+    ap.add_argument("--ema-tau", type=float, default=0.0, help="warm-up of --ema-decay: decay * (1 - exp(-updates / tau)); 0: none")
+    ap.add_argument("--seed", type=int, default=None, help="seed of torch, numpy, random and the loaders (every epoch starts from (seed, epoch))")
+    ap.add_argument("--deterministic", action="store_true", help="EngineConfig.DETERMINISTIC: bit-reproducible steps (the new kernels use no atomics anyway)")
+    ap.add_argument("--checkpoint-dir", default="checkpoints_pretrain")
+    ap.add_argument("--save-frequency", type=int, default=10)
+    ap.add_argument("--resume", default=None)
+    a = ap.parse_args()
+    if bool(a.synthetic) == bool(a.data_root):
+        ap.error("give exactly one of --data-root and --synthetic")
+    if not 0.0 <= a.label_smoothing < 1.0:
+        ap.error("--label-smoothing must lie in [0, 1)")
+    if a.image_size < 32 or a.image_size % 32:
+        ap.error("--image-size must be a multiple of 32 (the trunk halves the map five times)")
+    if a.deterministic:
+        from yolo.config import CONFIG
+        CONFIG.DETERMINISTIC = True
+        if a.seed is None:
+            a.seed = 0
+    gen, worker_init = None, None
+    if a.seed is not None:
+        seed_epoch(a.seed, 0)                 # parameter initialisation
+        gen = torch.Generator()
+        gen.manual_seed(a.seed)
+        worker_init = _seed_worker
+
+    device = a.device
+    if a.synthetic:
+        classes = a.num_classes or 10
+        train_ds = SyntheticClassificationDataset(a.synthetic, classes, a.image_size, seed=0, train=True)
+        val_ds = SyntheticClassificationDataset(max(min(a.batch_size, a.synthetic), a.synthetic // 8), classes, a.image_size, seed=1, train=False)
+        val_ds.patterns = train_ds.patterns          # the same classes, other samples
+    else:
+        train_ds = ImageFolderClassification(a.data_root, "train", a.image_size)
+        val_ds = ImageFolderClassification(a.data_root, "val", a.image_size, classes=train_ds.classes)
+        classes = len(train_ds.classes)
+        if a.num_classes is not None and a.num_classes != classes:
+            ap.error(f"--num-classes {a.num_classes}, but {a.data_root}/train holds {classes} class directories")
+    pin = device == "cuda"
+    train_loader = DataLoader(train_ds, batch_size=a.batch_size, shuffle=True, num_workers=a.num_workers, pin_memory=pin,
+                              drop_last=len(train_ds) >= a.batch_size, generator=gen, worker_init_fn=worker_init)
+    val_loader = DataLoader(val_ds, batch_size=a.batch_size, shuffle=False, num_workers=a.num_workers, pin_memory=pin, worker_init_fn=worker_init)
+
+    model = YOLOv1Classifier(num_classes=classes).to(device)
+    criterion = SoftmaxCrossEntropy(label_smoothing=a.label_smoothing)
+    params = [p for p in model.parameters() if p.requires_grad]
+    if device == "cuda":
+        from yolo.optim import SGD, Adam     # fused clip(10) + Adam / SGD with momentum on the HIP kernels
+        if a.optimizer == "sgd":
+            optimizer = SGD(params, lr=a.lr, momentum=a.momentum, weight_decay=a.weight_decay, nesterov=a.nesterov, max_grad_norm=10.0)
+        else:
+            optimizer = Adam(params, lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=10.0)
+        optimizer.attach_plan(model.head_plan())      # the Linear layer's bf16 operand is refreshed by the pass that updates its master
+    elif a.optimizer == "sgd":
+        optimizer = torch.optim.SGD(params, lr=a.lr, momentum=a.momentum, weight_decay=a.weight_decay, nesterov=a.nesterov)
+    else:
+        optimizer = torch.optim.Adam(params, lr=a.lr, weight_decay=a.weight_decay)
+    scheduler = torch.optim.lr_scheduler.MultiStepLR(optimizer, milestones=[int(e) for e in a.lr_decay_epochs.split(",")], gamma=0.1)
+
+    start_epoch, best_top1 = 1, None
+    if a.resume:
+        ck = torch.load(a.resume, map_location=device, weights_only=True)
+        if ck.get("num_classes", classes) != classes:
+            ap.error(f"--resume {a.resume} was trained with {ck['num_classes']} classes, this run has {classes}")
+        model.load_state_dict(ck["model_state_dict"])
+        optimizer.load_state_dict(ck["optimizer_state_dict"])
+        if "scheduler_state_dict" in ck:
+            scheduler.load_state_dict(ck["scheduler_state_dict"])
+        start_epoch = ck["epoch"] + 1
+        best_top1 = ck.get("val_top1")
+    ema = None
+    if a.ema_decay is not None:
+        from yolo.optim import ModelEMA
+        ema = ModelEMA(model, decay=a.ema_decay, tau=a.ema_tau, optimizer=optimizer if device == "cuda" else None)
+        if a.resume and "ema_state_dict" in ck:
+            ema.load_state_dict({"module": ck["ema_state_dict"], "updates": ck.get("ema_updates", 0), "decay": a.ema_decay, "tau": a.ema_tau})
+
+    ckdir = Path(a.checkpoint_dir)
+    ckdir.mkdir(parents=True, exist_ok=True)
+    record = {"num_classes": classes, "image_size": a.image_size}
+    if a.seed is not None:
+        record.update(seed=a.seed, deterministic=bool(a.deterministic))
+    res = loop.train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, a.epochs, ckdir, save_frequency=a.save_frequency,
+                     start_epoch=start_epoch, best_top1_init=best_top1, seed=a.seed, record=record, ema=ema)
+    print("done:", res)
+
+
+if __name__ == "__main__":
+    main()

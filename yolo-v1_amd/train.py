@@ -6,7 +6,8 @@
 
 Defaults follow src/train.py:269-338: batch 64, lr 1e-4, weight decay 5e-4, LR decay x0.1 at epochs
 75 and 105, lambda_coord 5, lambda_noobj 0.5.  ``--backbone`` is additive (the reference hard-codes
-ResNet50, which needs torchvision); ``--synthetic N`` trains on N random images instead of PASCAL VOC.
+ResNet50, which needs torchvision); ``--synthetic N`` trains on N random images instead of PASCAL VOC;
+``--backbone yolov1 --backbone-weights PATH`` starts from a trunk that pretrain.py trained as a classifier (the paper's first stage).
 """
 
 from __future__ import annotations
@@ -77,12 +78,18 @@ def main():
     ap.add_argument("--accum-steps", type=int, default=1,
                     help="gradient accumulation: K batches per optimizer step and per all-reduce -- effective batch = batch-size x K x world; a last "
                          "group of an epoch with fewer than K batches is dropped.  Default 1: none")
+    ap.add_argument("--backbone-weights", default=None,
+                    help="--backbone yolov1 only: a classification checkpoint of pretrain.py whose trunk (features.N.*) initialises the backbone "
+                         "(YOLOv1Backbone.load_pretrained); --resume wins over it.  Default: random initialisation")
+    ap.add_argument("--use-ema", action="store_true", help="with --backbone-weights: take the checkpoint's averaged weights (ema_state_dict) when it has them")
     ap.add_argument("--seed", type=int, default=None, help="seed of torch, numpy, random and the loaders (every epoch starts from (seed, epoch))")
     a = ap.parse_args()
     if a.accum_steps < 1:
         ap.error("--accum-steps must be at least 1")
     if a.augment != "reference" and a.synthetic:
         ap.error("--augment needs the VOC datasets (synthetic samples are not augmented)")
+    if a.backbone_weights and a.backbone != "yolov1":
+        ap.error("--backbone-weights needs --backbone yolov1 (a classification checkpoint of pretrain.py holds that trunk)")
     if a.deterministic:
         if a.backbone == "resnet50":
             # (the training loop puts the whole model in train(): there is no eval-mode trunk to ask for here)
@@ -128,6 +135,13 @@ def main():
                             worker_init_fn=worker_init)
 
     backbone = YOLOv1Backbone() if a.backbone == "yolov1" else ResNetBackbone(pretrained=not a.no_pretrained, freeze=a.freeze_backbone)
+    if a.backbone_weights and not a.resume:
+        ck0 = torch.load(a.backbone_weights, map_location="cpu", weights_only=True)
+        sd = ck0["ema_state_dict"] if (a.use_ema and "ema_state_dict" in ck0) else ck0["model_state_dict"]
+        loaded = backbone.load_pretrained(sd)
+        if rank == 0:
+            print(f"backbone: loaded {loaded} tensors from {a.backbone_weights}" + (" (averaged weights)" if sd is not ck0["model_state_dict"] else ""))
+        del ck0, sd
     model = YOLOv1(backbone=backbone, num_classes=20, S=7, B=2).to(device)
     if world > 1:
         broadcast_parameters(model)

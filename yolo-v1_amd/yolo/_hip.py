@@ -198,6 +198,9 @@ _SIGS = {
     "yolo_ema_update_multi_bg": [ctypes.POINTER(EmaTensor), c_int, c_float, c_void_p, c_int, c_void_p],
     "yolo_grad_accum": [c_void_p, c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p],
     "yolo_grad_accum_multi": [ctypes.POINTER(AccumTensor), c_int, c_float, c_void_p, c_void_p],
+    "yolo_gap_fwd": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "yolo_gap_bwd": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
+    "yolo_softmax_xent_fwd_bwd": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "yolo_bias_lrelu_rows": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
     "yolo_bias_lrelu_rows_slabs": [c_void_p, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p],
 }

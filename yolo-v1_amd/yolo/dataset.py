@@ -458,3 +458,83 @@ def create_voc_datasets(years_and_splits: list, download: bool = True, S: int = 
                                  device_transform=device_transform, recipe=recipe)
                 for y, s in years_and_splits]
     return datasets[0] if len(datasets) == 1 else CombinedVOCDataset(datasets)
+
+
+# ------------------------------------------------------------------------------------------------------------------
+# Classification pretraining (pretrain.py): image folders and a synthetic stand-in.  Extension of the reference surface.
+# ------------------------------------------------------------------------------------------------------------------
+IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp", ".ppm", ".webp")
+
+
+class _ClassifyTransform:
+    """PIL image -> normalised (3, size, size) tensor.  Training: the geometry and colour of ``_Augment`` (no boxes) and a horizontal flip with
+    probability 1/2, all drawn from torch's global generator; validation: the Resize of ``inference._Preprocess``."""
+
+    def __init__(self, size: int, train: bool):
+        from .inference import _Preprocess
+        self.train = train
+        self.augment = _Augment((size, size)) if train else None
+        self.finish = _Preprocess(size=(size, size))          # Resize (a no-op behind the crop) + ToTensor + Normalize
+
+    def __call__(self, image: Image.Image) -> torch.Tensor:
+        if self.train:
+            image, _ = self.augment(image, [])
+            if float(torch.rand(1).item()) < 0.5:
+                image = image.transpose(Image.FLIP_LEFT_RIGHT)
+        return self.finish(image)
+
+
+class ImageFolderClassification(Dataset):
+    """``<root>/<split>/<class>/*`` image folders: the classes are the sorted directory names of the split, a sample is
+    (normalised (3, size, size) tensor, class index).  Pillow only.  ``classes``: the class list of another split (the validation split of a
+    training run uses the training split's indices; a directory it does not name is an error)."""
+
+    def __init__(self, root: str | Path, split: str = "train", size: int = 224, train: bool | None = None, classes: List[str] | None = None):
+        self.dir = Path(root) / split
+        if not self.dir.is_dir():
+            raise FileNotFoundError(f"no directory {self.dir}: expected <root>/{split}/<class>/<image files>")
+        found = sorted(d.name for d in self.dir.iterdir() if d.is_dir())
+        if not found:
+            raise FileNotFoundError(f"{self.dir} holds no class directories")
+        self.classes = list(classes) if classes is not None else found
+        self.class_to_idx = {n: i for i, n in enumerate(self.classes)}
+        unknown = [n for n in found if n not in self.class_to_idx]
+        if unknown:
+            raise ValueError(f"{self.dir}: class directories {unknown[:5]} are not among the given classes")
+        self.samples = [(p, self.class_to_idx[n]) for n in found for p in sorted((self.dir / n).iterdir())
+                        if p.suffix.lower() in IMAGE_EXTENSIONS]
+        if not self.samples:
+            raise FileNotFoundError(f"{self.dir} holds no images ({', '.join(IMAGE_EXTENSIONS)})")
+        self.transform = _ClassifyTransform(size, split == "train" if train is None else train)
+
+    def __len__(self) -> int:
+        return len(self.samples)
+
+    def __getitem__(self, idx: int):
+        path, label = self.samples[idx]
+        return self.transform(Image.open(path).convert("RGB")), label
+
+
+class SyntheticClassificationDataset(Dataset):
+    """``length`` images of ``num_classes`` learnable classes without a dataset on disk: sample ``idx`` has class ``idx % num_classes``, and an image is
+    its class's fixed low-resolution colour pattern (8 x 8 blocks, drawn once from ``seed``) plus per-sample noise (from ``(seed, idx)``), as
+    uint8 RGB through the same Pillow transforms as the folder dataset."""
+
+    def __init__(self, length: int = 256, num_classes: int = 10, size: int = 224, seed: int = 0, train: bool = False, noise: float = 24.0):
+        self.length, self.num_classes, self.size, self.seed, self.noise = length, num_classes, size, seed, noise
+        rng = np.random.Generator(np.random.PCG64([seed, 1 << 20]))
+        self.patterns = rng.integers(32, 224, (num_classes, 8, 8, 3)).astype(np.float32)
+        self.transform = _ClassifyTransform(size, train)
+
+    def __len__(self) -> int:
+        return self.length
+
+    def image(self, idx: int) -> Image.Image:
+        rng = np.random.Generator(np.random.PCG64([self.seed, idx]))
+        rep = -(-self.size // 8)
+        base = np.kron(self.patterns[idx % self.num_classes], np.ones((rep, rep, 1), dtype=np.float32))[: self.size, : self.size]
+        arr = base + rng.standard_normal(base.shape, dtype=np.float32) * self.noise
+        return Image.fromarray(np.clip(arr, 0, 255).astype(np.uint8), "RGB")
+
+    def __getitem__(self, idx: int):
+        return self.transform(self.image(idx)), idx % self.num_classes

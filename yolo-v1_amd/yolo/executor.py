@@ -55,7 +55,7 @@ class Layer:
 
 
 class Plan:
-    """Executable plan for [conv|pool]* [flatten fc*]? ."""
+    """Executable plan for [conv|pool]* [flatten fc*]? (with no conv / pool in front, the input is the feature map that nn.Flatten flattens)."""
 
     SLOPE = 0.1
 
@@ -683,6 +683,8 @@ class Plan:
         self._bwd_seed(b, li, gout)
         step = {"fc": self._bwd_fc, "pool": self._bwd_pool, "conv": self._bwd_conv}
         while li >= 0:
+            if li == 0 and self.layers[0].kind == "flatten":
+                break             # a plan that starts with nn.Flatten (a pooled 1 x 1 map into a Linear layer): b.g_flat is the input's gradient already
             assert self.layers[li].kind != "flatten", "nn.Flatten is handled together with the Linear layer behind it"
             li -= step[self.layers[li].kind](b, li)       # (the Linear behind nn.Flatten consumes both)
         return self._finish_backward(b)
@@ -914,13 +916,16 @@ class Plan:
     def _finish_backward(self, b):
         """join the streams, the gradient wrt the plan's input if asked for, the workspace back to its pool, gradients to the arena's owner or to autograd"""
         L = self.layers[0]
-        assert L.kind == "conv", "plans start with a conv layer"
+        assert L.kind in ("conv", "flatten"), "plans start with a conv layer or with nn.Flatten"
         if b.side_t is not None:
             b.main_t.wait_stream(b.side_t)       # every weight gradient is final before anything that follows the backward pass
             if self.arena is not None and self.on_stream_wait is not None:
                 self.on_stream_wait(b.main_t.cuda_stream, b.side_t.cuda_stream)
         gx = None
-        if b.need_gx:
+        if b.need_gx and L.kind == "flatten":
+            a = b.ws["in"]            # nn.Flatten keeps the NCHW order of the plan's fp32 input: the rows of the Linear layer's data gradient are that tensor
+            gx = b.g_flat.view(b.N, a.C, a.H, a.W)
+        elif b.need_gx:
             gx = (self._stem_dgrad if L.first else self._dgrad_to_input)(0, b.g_act, b.N, b.dev, b.st)
         if self.debug_keep:
             self.last = (b.ws, b.fc_saved)

@@ -95,6 +95,28 @@ class YOLOv1Backbone(_PlanOwner, Backbone):
             self._plan = engine.Plan.from_modules(self.features, 3, True)
         return self._own(self._plan)
 
+    @torch.no_grad()
+    def load_pretrained(self, state_dict) -> int:
+        """Take over the trunk of a classification checkpoint (``yolo.classify.YOLOv1Classifier``, pretrain.py): every
+        ``features.N.weight`` / ``features.N.bias`` of ``state_dict`` is copied into layer N of this backbone; its other entries (the classifier's
+        ``fc.*``) are ignored, and the layers the checkpoint does not hold -- the four convolutions detection adds -- stay as initialised.
+        A tensor of another shape, or a layer this backbone does not have, raises naming the key.  Returns the number of tensors loaded
+        (40 for the paper's 20 convolutions).  Extension of the reference surface, which pretrains nothing."""
+        own = dict(self.named_parameters())
+        todo = []
+        for key, src in state_dict.items():
+            if not key.startswith("features."):
+                continue
+            dst = own.get(key)
+            if dst is None:
+                raise KeyError(f"load_pretrained: {key} is not a parameter of YOLOv1Backbone")
+            if tuple(dst.shape) != tuple(src.shape):
+                raise ValueError(f"load_pretrained: {key} has shape {tuple(src.shape)} in the checkpoint, the backbone expects {tuple(dst.shape)}")
+            todo.append((dst, src))
+        for dst, src in todo:          # nothing is copied unless everything fits
+            dst.copy_(src)
+        return len(todo)
+
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.is_cuda:
             return engine.run_plan(self.hip_plan(), x, self.training)
