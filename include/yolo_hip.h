@@ -452,6 +452,9 @@ typedef struct yolo_adam_tensor {
     void *p_bf16;        /* optional bf16 shadow of p in the same layout (NULL: none) */
     long n;              /* elements */
 } yolo_adam_tensor;
+/* *acc += the sum of squares of every g[i] (n[i] elements; empty tensors are legal): one launch per YOLO_MT_MAX tensors.
+ * YOLO_E_ARG: a null pointer, count < 0, n[i] < 0.  YOLO_E_UNSUPPORTED: a g[i] not 16-B aligned.  Every tensor is checked before the first
+ * launch.  Either way nothing is launched. */
 int yolo_sumsq_f32_multi(const float *const *g, const long *n, int count, double *acc, yolo_stream_t stream);
 /* Order-fixed forms of yolo_sumsq_f32 / yolo_sumsq_f32_multi (norm_fixed.hip; EngineConfig.DETERMINISTIC).  They replace the one fp64
  * atomicAdd per workgroup in which sumsq_kernel / sumsq_multi_kernel end: a workgroup owns one 65536-element slice of one tensor (the
@@ -463,6 +466,9 @@ int yolo_sumsq_fixed_slots(const long *n, int count, long *slots);
 int yolo_sumsq_f32_fixed(const float *g, long n, double *scratch, long scratch_slots, double *acc, yolo_stream_t stream);
 int yolo_sumsq_f32_multi_fixed(const float *const *g, const long *n, int count, double *scratch, long scratch_slots, double *acc,
                                yolo_stream_t stream);
+/* yolo_adam_step for a whole parameter list: one launch per YOLO_MT_MAX tensors; empty tensors are legal.
+ * YOLO_E_ARG: a null pointer, count < 0, step < 1, n < 0.  YOLO_E_UNSUPPORTED: p / g / m / v not 16-B aligned, p_bf16 not 8-B aligned.
+ * Every tensor is checked before the first launch.  Either way nothing is launched. */
 int yolo_adam_step_multi(const yolo_adam_tensor *t, int count, float lr, float beta1, float beta2, float eps,
                          float weight_decay, long step, const double *norm_sq, float max_norm, const float *skip_flag,
                          yolo_stream_t stream);

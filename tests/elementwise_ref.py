@@ -43,7 +43,7 @@ def adam_constants(lr, beta1, beta2, eps, wd, step, exact_constants=False):
 
 
 def clip_ref(norm_sq, max_norm) -> float:
-    """the clip coefficient of adam_kernel / adam_multi_kernel / adam_multi_bg_kernel / scale_by_clip_kernel, bit for bit:
+    """the clip coefficient of every optimizer kernel (clip_coefficient in csrc/multi_tensor.h; scale_by_clip_kernel: clip_ratio), bit for bit:
     total = (float)sqrt(double norm_sq); c = max_norm / (total + 1e-6f) in fp32; min(1, c).  norm_sq None (NULL): 1"""
     if norm_sq is None:
         return 1.0

@@ -64,6 +64,16 @@ def test_struct_layouts_match_the_header():
     assert sizes == [ctypes.sizeof(_hip.IgemmDesc), ctypes.sizeof(_hip.WgradDesc), ctypes.sizeof(_hip.PoolDesc)]
 
 
+def test_constants_match_the_header():
+    """the #defines the Python side restates: tensors per multi-tensor launch, replicas of the BatchNorm accumulators"""
+    from yolo import _hip
+    src = open(HEADER).read()
+    define = lambda name: int(re.search(rf"^#define {name} (\d+)$", src, flags=re.M).group(1))
+    assert _hip.MT_MAX == define("YOLO_MT_MAX")
+    assert _hip.BN_ACC_REPLICAS == define("YOLO_BN_ACC_REPLICAS")
+    assert _hip.ABI_VERSION == define("YOLO_HIP_ABI_VERSION")
+
+
 def test_gpu_tensor_without_library_fails_loudly(monkeypatch):
     from yolo import _hip
     monkeypatch.setattr(_hip, "_LIB", None)

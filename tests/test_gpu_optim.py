@@ -339,3 +339,44 @@ def test_adam_entries_reject_bad_arguments():
         assert L.yolo_adam_step_multi_bg(ok, 2, *h, 1, None, MAX_NORM, None, wg, st) == E_ARG
     torch.cuda.synchronize()
     assert all(bool((t == 1).all()) for t in x) and not bool(sh.any())
+
+
+def _table49_with_misaligned_entry_48():
+    """49 tensors, one more than a launch takes -> sizes, inputs and, for the last one, a gradient that starts 4 bytes behind a 16-B boundary"""
+    pool = [5, 8193, 1, 1027, 0, 4, 8192]
+    sizes = [pool[i % len(pool)] for i in range(49)]
+    ins = _inputs(sizes, 600)
+    g48 = torch.cat([ins[48][1].new_zeros(1), ins[48][1]])[1:]
+    assert g48.data_ptr() % 16 == 4 and g48.numel() == sizes[48] == 8192
+    return sizes, ins, g48
+
+
+def test_adam_multi_checks_every_tensor_before_the_first_launch():
+    """tensor 48 is refused: the 48 tensors of the first launch keep the bits of p, exp_avg and exp_avg_sq"""
+    from yolo._hip import AdamTensor, E_UNSUPPORTED
+    sizes, ins, g48 = _table49_with_misaligned_entry_48()
+    bufs = [(Guarded(p), Guarded(m), Guarded(v)) for p, _, m, v in ins]
+    gs = [_gbuf(g) for _, g, _, _ in ins[:48]]
+    gptr = [g._base_ptr for g in gs] + [g48.data_ptr()]
+    tab = (AdamTensor * 49)(*[AdamTensor(P.ptr, gp, M.ptr, V.ptr, None, P.n) for (P, M, V), gp in zip(bufs, gptr)])
+    h = (HYPER["lr"], HYPER["beta1"], HYPER["beta2"], HYPER["eps"], HYPER["wd"])
+    rc = _lib().yolo_adam_step_multi(tab, 49, *h, 1, None, MAX_NORM, None, _stream())
+    assert rc == E_UNSUPPORTED and "tensor 48" in _last_error(), (rc, _last_error())
+    torch.cuda.synchronize()
+    for i, ((P, M, V), (p, _, m, v)) in enumerate(zip(bufs, ins)):
+        for B, src in ((P, p), (M, m), (V, v)):
+            assert torch.equal(B.t.view(torch.int32), src.view(torch.int32)) and B.guards_ok(), f"tensor {i} (n={P.n}) was written by a refused call"
+
+
+def test_sumsq_multi_checks_every_tensor_before_the_first_launch():
+    """the same table: the accumulator keeps its 3.25"""
+    from yolo._hip import E_UNSUPPORTED
+    sizes, ins, g48 = _table49_with_misaligned_entry_48()
+    gs = [_gbuf(g) for _, g, _, _ in ins[:48]]
+    ptrs = (ctypes.c_void_p * 49)(*[g._base_ptr for g in gs], g48.data_ptr())
+    ns = (ctypes.c_long * 49)(*sizes)
+    acc = Guarded(torch.tensor([3.25], dtype=torch.float64, device="cuda").view(torch.float32))
+    rc = _lib().yolo_sumsq_f32_multi(ptrs, ns, 49, acc.ptr, _stream())
+    assert rc == E_UNSUPPORTED and "tensor 48" in _last_error(), (rc, _last_error())
+    torch.cuda.synchronize()
+    assert float(acc.t.view(torch.float64)[0]) == 3.25 and acc.guards_ok(), "a refused call added the first launch's tensors"

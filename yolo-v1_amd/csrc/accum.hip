@@ -6,18 +6,12 @@
 // and contraction is off, so the single and the multi-tensor form compute the same bits.
 // dst may be exactly x or exactly y (the in-place uses: acc = fmaf(alpha, g, acc) and the fold g = fmaf(alpha, g, acc)): a lane reads its
 // elements before it writes them and no other lane touches them.  8 B per element without y, 12 B with it.
-// Launch shape of ema_multi_kernel: a workgroup owns one MT_CHUNK slice of one tensor of the table in the kernel arguments.
-#include "optim_common.h"
+// Foreground launch shape of multi_tensor.h: a workgroup owns one MT_CHUNK slice of one tensor of the table in the kernel arguments.
+#include "multi_tensor.h"
 
 #include <cmath>
 
 namespace yolo {
-
-struct AccumTable {
-    yolo_accum_tensor t[YOLO_MT_MAX];
-    int first[YOLO_MT_MAX + 1];       // first chunk of every tensor
-    int count;
-};
 
 __device__ __forceinline__ float accum1(float x, float y, float alpha)
 {
@@ -41,13 +35,11 @@ __device__ __forceinline__ float4 scale4(const float4 &x, float alpha)
     return make_float4(scale1(x.x, alpha), scale1(x.y, alpha), scale1(x.z, alpha), scale1(x.w, alpha));
 }
 
-__global__ void __launch_bounds__(256) accum_multi_kernel(const AccumTable tab, float alpha, const float *skip_flag)
+__global__ void __launch_bounds__(256) accum_multi_kernel(const MtTable<yolo_accum_tensor> tab, float alpha, const float *skip_flag)
 {
-    if (skip_flag && *skip_flag != 0.0f) return;        // the producer of the gradients flagged its input: nothing is written
-    const int ti = find_tensor(tab.first, tab.count, blockIdx.x);
-    const yolo_accum_tensor &t = tab.t[ti];
-    const long beg = (long)(blockIdx.x - tab.first[ti]) * MT_CHUNK;
-    const long end = min(t.n, beg + MT_CHUNK);
+    if (mt_skipped(skip_flag)) return;
+    long beg, end;
+    const yolo_accum_tensor &t = mt_slice<MT_CHUNK>(tab, beg, end);
     const bool has_y = t.y != nullptr;                  // uniform over the workgroup
     if (beg + MT_CHUNK <= t.n) {
         // a whole chunk: all 16-B loads of a lane (sixteen with y, eight without) are issued before the first store
@@ -112,33 +104,13 @@ static int accum_tensor_ok(const char *who, const yolo_accum_tensor &a, int idx)
     return 0;
 }
 
-// every tensor of the call is checked before the first launch: a refused call launches nothing
 static int accum_launch(const char *who, const yolo_accum_tensor *t, int count, float alpha, const float *skip_flag, yolo_stream_t stream)
 {
     if (!std::isfinite(alpha)) return fail(YOLO_E_ARG, "%s: alpha %g is not finite", who, (double)alpha);
-    for (int i = 0; i < count; ++i) {
-        if (int rc = accum_tensor_ok(who, t[i], i)) return rc;
-        if ((t[i].n + MT_CHUNK - 1) / MT_CHUNK > 0x7fffffffL) return fail(YOLO_E_UNSUPPORTED, "%s: tensor %d is too large", who, i);
-    }
-    for (int base = 0; base < count;) {
-        AccumTable tab{};
-        long chunks = 0;
-        int k = 0;
-        for (; base + k < count && k < YOLO_MT_MAX; ++k) {
-            const long c = (t[base + k].n + MT_CHUNK - 1) / MT_CHUNK;
-            if (chunks + c > 0x7fffffffL) break;
-            tab.t[k] = t[base + k]; tab.first[k] = (int)chunks;
-            chunks += c;
-        }
-        tab.first[k] = (int)chunks;
-        tab.count = k;
-        if (chunks > 0) {
-            hipLaunchKernelGGL(accum_multi_kernel, dim3((unsigned)chunks), dim3(256), 0, STRM(stream), tab, alpha, skip_flag);
-            if (int rc = check_launch(who)) return rc;
-        }
-        base += k;
-    }
-    return 0;
+    return mt_foreground<MT_CHUNK>(who, t, count, accum_tensor_ok, [&](const MtTable<yolo_accum_tensor> &tab, long chunks) {
+        hipLaunchKernelGGL(accum_multi_kernel, dim3((unsigned)chunks), dim3(256), 0, STRM(stream), tab, alpha, skip_flag);
+        return check_launch(who);
+    });
 }
 
 YOLO_API int yolo_grad_accum(float *dst, const float *x, const float *y, long n, float alpha, const float *skip_flag, yolo_stream_t stream)

@@ -8,17 +8,9 @@
 // 12 B per element: read e and p, write e.  p is never written.
 // Same launch shapes as the SGD entries: a workgroup owns one MT_CHUNK slice of one tensor of the table in the kernel arguments
 // (yolo_ema_update, yolo_ema_update_multi), or `workgroups` persistent 1024-thread workgroups walk the chunk list (yolo_ema_update_multi_bg).
-#include "optim_common.h"
-
-#include <algorithm>
+#include "multi_tensor.h"
 
 namespace yolo {
-
-struct EmaTable {
-    yolo_ema_tensor t[YOLO_MT_MAX];
-    int first[YOLO_MT_MAX + 1];       // first chunk of every tensor
-    int count;
-};
 
 __device__ __forceinline__ float ema1(float e, float p, float w)
 {
@@ -32,25 +24,33 @@ __device__ __forceinline__ float4 ema4(const float4 &e, const float4 &p, float w
     return make_float4(ema1(e.x, p.x, w), ema1(e.y, p.y, w), ema1(e.z, p.z, w), ema1(e.w, p.w, w));
 }
 
-// false: the optimizer skipped this step on the device, and a skipped step is no EMA step either
-__device__ __forceinline__ bool ema_begin(const float *skip_flag)
-{
-    return !(skip_flag && *skip_flag != 0.0f);
-}
+// The element op of the background kernel (multi_tensor.h: mt_walk_bg); the foreground kernel shares its tail
+struct EmaOp {
+    float w;
+    struct Vals {
+        float4 e[2], p[2];
+    };
+    __device__ __forceinline__ void load(const yolo_ema_tensor &t, long i, int u, Vals &x) const
+    {
+        x.e[u] = *reinterpret_cast<const float4 *>(t.ema + i);
+        x.p[u] = *reinterpret_cast<const float4 *>(t.p + i);
+    }
+    __device__ __forceinline__ void full(const yolo_ema_tensor &t, long i, int u, Vals &x) const
+    {
+        *reinterpret_cast<float4 *>(t.ema + i) = ema4(x.e[u], x.p[u], w);
+    }
+    __device__ __forceinline__ void tail(const yolo_ema_tensor &t, long k0, long end, long step) const
+    {
+        for (long k = k0; k < end; k += step) t.ema[k] = ema1(t.ema[k], t.p[k], w);
+    }
+};
 
-// elements [k0, end) of one tensor, one per thread and trip: the partial chunk behind a tensor's last float4 / last full chunk
-__device__ __forceinline__ void ema_scalar(const yolo_ema_tensor &t, long k0, long end, long step, float w)
+// a skipped optimizer step (skip_flag) is no EMA step either
+__global__ void __launch_bounds__(256) ema_multi_kernel(const MtTable<yolo_ema_tensor> tab, float w, const float *skip_flag)
 {
-    for (long k = k0; k < end; k += step) t.ema[k] = ema1(t.ema[k], t.p[k], w);
-}
-
-__global__ void __launch_bounds__(256) ema_multi_kernel(const EmaTable tab, float w, const float *skip_flag)
-{
-    if (!ema_begin(skip_flag)) return;
-    const int ti = find_tensor(tab.first, tab.count, blockIdx.x);
-    const yolo_ema_tensor &t = tab.t[ti];
-    const long beg = (long)(blockIdx.x - tab.first[ti]) * MT_CHUNK;
-    const long end = min(t.n, beg + MT_CHUNK);
+    if (mt_skipped(skip_flag)) return;
+    long beg, end;
+    const yolo_ema_tensor &t = mt_slice<MT_CHUNK>(tab, beg, end);
     if (beg + MT_CHUNK <= t.n) {
         // a whole chunk: all sixteen 16-B loads of a lane are issued before the first result is used (64 KB in flight per workgroup)
         float4 ev[8], pv[8];
@@ -73,61 +73,15 @@ __global__ void __launch_bounds__(256) ema_multi_kernel(const EmaTable tab, floa
             const float4 pv = *reinterpret_cast<const float4 *>(t.p + i);
             *reinterpret_cast<float4 *>(t.ema + i) = ema4(ev, pv, w);
         } else {
-            ema_scalar(t, i, end, 1, w);
+            EmaOp{w}.tail(t, i, end, 1);
         }
     }
 }
 
-// Background form: the structure of sgd_multi_bg_kernel (sgd.hip) -- gridDim.x persistent workgroups of 1024 threads, each alone on its CU
-// because of the dynamic LDS it reserves and does not use; the loads of the NEXT chunk are issued before the current one is computed and
-// stored.
-__global__ void __launch_bounds__(1024) ema_multi_bg_kernel(const EmaTable tab, int chunks, float w, const float *skip_flag)
+__global__ void __launch_bounds__(1024) ema_multi_bg_kernel(const MtTable<yolo_ema_tensor> tab, int chunks, float w, const float *skip_flag)
 {
-    if (!ema_begin(skip_flag)) return;
-    struct Vals {
-        float4 e[2], p[2];
-    };
-    auto where = [&](int b, int &ti, long &beg, bool &full) {
-        ti = find_tensor(tab.first, tab.count, b);
-        beg = (long)(b - tab.first[ti]) * MT_CHUNK;
-        full = beg + MT_CHUNK <= tab.t[ti].n;
-    };
-    auto load = [&](int ti, long beg, Vals &x) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const long i = beg + (long)(u * 1024 + threadIdx.x) * 4;
-            x.e[u] = *reinterpret_cast<const float4 *>(tab.t[ti].ema + i);
-            x.p[u] = *reinterpret_cast<const float4 *>(tab.t[ti].p + i);
-        }
-    };
-    int b = blockIdx.x;
-    int ti = 0, nti = 0;
-    long beg = 0, nbeg = 0;
-    bool full = false, nfull = false;
-    Vals cur = {}, nxt = {};
-    if (b < chunks) {
-        where(b, ti, beg, full);
-        if (full) load(ti, beg, cur);
-    }
-    while (b < chunks) {
-        const int nb = b + (int)gridDim.x;
-        if (nb < chunks) {
-            where(nb, nti, nbeg, nfull);
-            if (nfull) load(nti, nbeg, nxt);
-        }
-        const yolo_ema_tensor &t = tab.t[ti];
-        if (full) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const long i = beg + (long)(u * 1024 + threadIdx.x) * 4;
-                *reinterpret_cast<float4 *>(t.ema + i) = ema4(cur.e[u], cur.p[u], w);
-            }
-        } else {
-            ema_scalar(t, beg + threadIdx.x, min(t.n, beg + MT_CHUNK), 1024, w);     // last, partial chunk of a tensor
-        }
-        b = nb; ti = nti; beg = nbeg; full = nfull;
-        cur = nxt;
-    }
+    if (mt_skipped(skip_flag)) return;
+    mt_walk_bg(tab, chunks, EmaOp{w});
 }
 
 }  // namespace yolo
@@ -150,33 +104,13 @@ static int ema_tensor_ok(const char *who, const yolo_ema_tensor &e, int idx)
     return 0;
 }
 
-// every tensor of the call is checked before the first launch: a refused call launches nothing
 static int ema_foreground(const char *who, const yolo_ema_tensor *t, int count, float w, const float *skip_flag, yolo_stream_t stream)
 {
     if (int rc = ema_weight_ok(who, w)) return rc;
-    for (int i = 0; i < count; ++i) {
-        if (int rc = ema_tensor_ok(who, t[i], i)) return rc;
-        if ((t[i].n + MT_CHUNK - 1) / MT_CHUNK > 0x7fffffffL) return fail(YOLO_E_UNSUPPORTED, "%s: tensor %d is too large", who, i);
-    }
-    for (int base = 0; base < count;) {
-        EmaTable tab{};
-        long chunks = 0;
-        int k = 0;
-        for (; base + k < count && k < YOLO_MT_MAX; ++k) {
-            const long c = (t[base + k].n + MT_CHUNK - 1) / MT_CHUNK;
-            if (chunks + c > 0x7fffffffL) break;
-            tab.t[k] = t[base + k]; tab.first[k] = (int)chunks;
-            chunks += c;
-        }
-        tab.first[k] = (int)chunks;
-        tab.count = k;
-        if (chunks > 0) {
-            hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)chunks), dim3(256), 0, STRM(stream), tab, w, skip_flag);
-            if (int rc = check_launch(who)) return rc;
-        }
-        base += k;
-    }
-    return 0;
+    return mt_foreground<MT_CHUNK>(who, t, count, ema_tensor_ok, [&](const MtTable<yolo_ema_tensor> &tab, long chunks) {
+        hipLaunchKernelGGL(ema_multi_kernel, dim3((unsigned)chunks), dim3(256), 0, STRM(stream), tab, w, skip_flag);
+        return check_launch(who);
+    });
 }
 
 YOLO_API int yolo_ema_update(float *ema, const float *p, long n, float w, const float *skip_flag, yolo_stream_t stream)
@@ -194,30 +128,11 @@ YOLO_API int yolo_ema_update_multi(const yolo_ema_tensor *t, int count, float w,
 YOLO_API int yolo_ema_update_multi_bg(const yolo_ema_tensor *t, int count, float w, const float *skip_flag, int workgroups, yolo_stream_t stream)
 {
     const char *who = "yolo_ema_update_multi_bg";
-    if (!t || count < 0 || count > YOLO_MT_MAX || workgroups < 1 || workgroups > 256)
-        return fail(YOLO_E_ARG, "%s: bad argument (at most %d tensors, 1 .. 256 workgroups)", who, YOLO_MT_MAX);
     if (int rc = ema_weight_ok(who, w)) return rc;
-    EmaTable tab{};
-    long chunks = 0;
-    for (int k = 0; k < count; ++k) {
-        if (int rc = ema_tensor_ok(who, t[k], k)) return rc;
-        tab.t[k] = t[k]; tab.first[k] = (int)chunks;
-        chunks += (t[k].n + MT_CHUNK - 1) / MT_CHUNK;
-        if (chunks > 0x7fffffffL) return fail(YOLO_E_UNSUPPORTED, "%s: too many elements", who);
-    }
-    tab.first[count] = (int)chunks;
-    tab.count = count;
-    if (chunks == 0) return 0;
-    constexpr int BG_LDS = 96 * 1024;       // with 1024 threads: one such workgroup per CU, and no 128-KB conv workgroup beside it
-    static bool attr_done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void *)ema_multi_bg_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, BG_LDS);
-        if (e != hipSuccess) return fail((int)e, "%s: hipFuncSetAttribute(%d B LDS): %s", who, BG_LDS, hipGetErrorString(e));
-        attr_done[dev] = true;
-    }
-    const dim3 grid((unsigned)std::min<long>(workgroups, chunks)), block(1024);
-    hipLaunchKernelGGL(ema_multi_bg_kernel, grid, block, BG_LDS, STRM(stream), tab, (int)chunks, w, skip_flag);
+    static bool lds_done[64] = {};
+    MtBackground<yolo_ema_tensor> bg;
+    if (int rc = mt_background(who, t, count, workgroups, true, ema_tensor_ok, (const void *)ema_multi_bg_kernel, lds_done, bg)) return rc;
+    if (bg.grid == 0) return 0;
+    hipLaunchKernelGGL(ema_multi_bg_kernel, dim3(bg.grid), dim3(1024), BG_LDS, STRM(stream), bg.tab, bg.chunks, w, skip_flag);
     return check_launch(who);
 }

@@ -7,9 +7,7 @@
 // 18 B on the first step (buf is only written), 12 B without momentum (buf is not touched).
 // Same launch shapes as the Adam entries: a workgroup owns one MT_CHUNK slice of one tensor of the table in the kernel arguments
 // (yolo_sgd_step, yolo_sgd_step_multi), or `workgroups` persistent 1024-thread workgroups walk the chunk list (yolo_sgd_step_multi_bg).
-#include "optim_common.h"
-
-#include <algorithm>
+#include "multi_tensor.h"
 
 namespace yolo {
 
@@ -21,11 +19,6 @@ struct SgdArgs {
     const double *norm_sq;
     float max_norm;
     const float *skip_flag;
-};
-struct SgdTable {
-    yolo_sgd_tensor t[YOLO_MT_MAX];
-    int first[YOLO_MT_MAX + 1];       // first chunk of every tensor
-    int count;
 };
 
 // Every product that feeds a sum is an explicit fma and nothing else may contract: the three launch forms then compute the same bits
@@ -42,131 +35,70 @@ __device__ __forceinline__ void sgd1(float &p, float g, float &buf, float clip, 
     p = __builtin_fmaf(-a.lr, g, p);                                            // param.add_(grad, alpha=-lr)
 }
 
-// false: the producer of the gradients flagged this step as invalid, nothing is updated
-__device__ __forceinline__ bool sgd_begin(const SgdArgs &a, float &clip)
-{
-    if (a.skip_flag && *a.skip_flag != 0.0f) return false;
-    clip = 1.0f;
-    if (a.norm_sq) {
-        const float total = (float)sqrt(*a.norm_sq);
-        const float c = a.max_norm / (total + 1e-6f);
-        clip = c < 1.0f ? c : 1.0f;
-    }
-    return true;
-}
-
-__device__ __forceinline__ uint2 pack_bf16x4(const float4 &v)
-{
-    uint2 o;
-    o.x = (unsigned)f32_to_bf16(v.x) | ((unsigned)f32_to_bf16(v.y) << 16);
-    o.y = (unsigned)f32_to_bf16(v.z) | ((unsigned)f32_to_bf16(v.w) << 16);
-    return o;
-}
-
+// The element op of both SGD kernels (multi_tensor.h: mt_walk_bg)
 template <int MODE>
-__device__ __forceinline__ void sgd4(float4 &p, const float4 &g, float4 &b, float clip, const SgdArgs &a)
-{
-    sgd1<MODE>(p.x, g.x, b.x, clip, a);
-    sgd1<MODE>(p.y, g.y, b.y, clip, a);
-    sgd1<MODE>(p.z, g.z, b.z, clip, a);
-    sgd1<MODE>(p.w, g.w, b.w, clip, a);
-}
-
-// elements [k0, end) of one tensor, one per thread and trip: the partial chunk behind a tensor's last float4 / last full chunk
-template <int MODE>
-__device__ __forceinline__ void sgd_scalar(const yolo_sgd_tensor &t, long k0, long end, long step, float clip, const SgdArgs &a)
-{
-    bf16_t *pb = (bf16_t *)t.p_bf16;
-    for (long k = k0; k < end; k += step) {
-        float pk = t.p[k], bk = MODE == MOM_NEXT ? t.buf[k] : 0.0f;
-        sgd1<MODE>(pk, t.g[k], bk, clip, a);
-        t.p[k] = pk;
-        if (MODE != MOM_NONE) t.buf[k] = bk;
-        if (pb) pb[k] = f32_to_bf16(pk);
-    }
-}
-
-template <int MODE>
-__global__ void __launch_bounds__(256) sgd_multi_kernel(const SgdTable tab, const SgdArgs a)
-{
+struct SgdOp {
     float clip;
-    if (!sgd_begin(a, clip)) return;
-    const int ti = find_tensor(tab.first, tab.count, blockIdx.x);
-    const yolo_sgd_tensor &t = tab.t[ti];
-    const long beg = (long)(blockIdx.x - tab.first[ti]) * MT_CHUNK;
-    const long end = min(t.n, beg + MT_CHUNK);
+    const SgdArgs &a;
+    struct Vals {
+        float4 p[2], g[2], b[2];
+    };
+    // one float4 of every array, already in registers: update, store at element i
+    __device__ __forceinline__ void vec(const yolo_sgd_tensor &t, long i, float4 &p, const float4 &g, float4 &b) const
+    {
+        sgd1<MODE>(p.x, g.x, b.x, clip, a);
+        sgd1<MODE>(p.y, g.y, b.y, clip, a);
+        sgd1<MODE>(p.z, g.z, b.z, clip, a);
+        sgd1<MODE>(p.w, g.w, b.w, clip, a);
+        *reinterpret_cast<float4 *>(t.p + i) = p;
+        if (MODE != MOM_NONE) *reinterpret_cast<float4 *>(t.buf + i) = b;
+        if (t.p_bf16) *reinterpret_cast<uint2 *>((bf16_t *)t.p_bf16 + i) = pack_bf16x4(p);
+    }
+    __device__ __forceinline__ void load(const yolo_sgd_tensor &t, long i, int u, Vals &x) const
+    {
+        x.p[u] = *reinterpret_cast<const float4 *>(t.p + i);
+        x.g[u] = *reinterpret_cast<const float4 *>(t.g + i);
+        if (MODE == MOM_NEXT) x.b[u] = *reinterpret_cast<const float4 *>(t.buf + i);
+    }
+    __device__ __forceinline__ void full(const yolo_sgd_tensor &t, long i, int u, Vals &x) const { vec(t, i, x.p[u], x.g[u], x.b[u]); }
+    __device__ __forceinline__ void tail(const yolo_sgd_tensor &t, long k0, long end, long step) const
+    {
+        bf16_t *pb = (bf16_t *)t.p_bf16;
+        for (long k = k0; k < end; k += step) {
+            float pk = t.p[k], bk = MODE == MOM_NEXT ? t.buf[k] : 0.0f;
+            sgd1<MODE>(pk, t.g[k], bk, clip, a);
+            t.p[k] = pk;
+            if (MODE != MOM_NONE) t.buf[k] = bk;
+            if (pb) pb[k] = f32_to_bf16(pk);
+        }
+    }
+};
+
+template <int MODE>
+__global__ void __launch_bounds__(256) sgd_multi_kernel(const MtTable<yolo_sgd_tensor> tab, const SgdArgs a)
+{
+    if (mt_skipped(a.skip_flag)) return;
+    const SgdOp<MODE> op{clip_coefficient(a.norm_sq, a.max_norm), a};
+    long beg, end;
+    const yolo_sgd_tensor &t = mt_slice<MT_CHUNK>(tab, beg, end);
     for (long i = beg + threadIdx.x * 4; i < end; i += 1024) {
         if (i + 4 <= end) {
             float4 pv = *reinterpret_cast<const float4 *>(t.p + i);
             const float4 gv = *reinterpret_cast<const float4 *>(t.g + i);
             float4 bv = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
             if (MODE == MOM_NEXT) bv = *reinterpret_cast<const float4 *>(t.buf + i);
-            sgd4<MODE>(pv, gv, bv, clip, a);
-            *reinterpret_cast<float4 *>(t.p + i) = pv;
-            if (MODE != MOM_NONE) *reinterpret_cast<float4 *>(t.buf + i) = bv;
-            if (t.p_bf16) *reinterpret_cast<uint2 *>((bf16_t *)t.p_bf16 + i) = pack_bf16x4(pv);
+            op.vec(t, i, pv, gv, bv);
         } else {
-            sgd_scalar<MODE>(t, i, end, 1, clip, a);
+            op.tail(t, i, end, 1);
         }
     }
 }
 
-// Background form: the structure of adam_multi_bg_kernel (optim.hip) -- gridDim.x persistent workgroups of 1024 threads, each alone on its CU
-// because of the dynamic LDS it reserves and does not use; the loads of the NEXT chunk are issued before the current one is computed and
-// stored, so that a CU keeps 100-200 KB in flight.
 template <int MODE>
-__global__ void __launch_bounds__(1024) sgd_multi_bg_kernel(const SgdTable tab, int chunks, const SgdArgs a)
+__global__ void __launch_bounds__(1024) sgd_multi_bg_kernel(const MtTable<yolo_sgd_tensor> tab, int chunks, const SgdArgs a)
 {
-    float clip;
-    if (!sgd_begin(a, clip)) return;
-    struct Vals {
-        float4 p[2], g[2], b[2];
-    };
-    auto where = [&](int b, int &ti, long &beg, bool &full) {
-        ti = find_tensor(tab.first, tab.count, b);
-        beg = (long)(b - tab.first[ti]) * MT_CHUNK;
-        full = beg + MT_CHUNK <= tab.t[ti].n;
-    };
-    auto load = [&](int ti, long beg, Vals &x) {
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-            const long i = beg + (long)(u * 1024 + threadIdx.x) * 4;
-            x.p[u] = *reinterpret_cast<const float4 *>(tab.t[ti].p + i);
-            x.g[u] = *reinterpret_cast<const float4 *>(tab.t[ti].g + i);
-            if (MODE == MOM_NEXT) x.b[u] = *reinterpret_cast<const float4 *>(tab.t[ti].buf + i);
-        }
-    };
-    int b = blockIdx.x;
-    int ti = 0, nti = 0;
-    long beg = 0, nbeg = 0;
-    bool full = false, nfull = false;
-    Vals cur = {}, nxt = {};
-    if (b < chunks) {
-        where(b, ti, beg, full);
-        if (full) load(ti, beg, cur);
-    }
-    while (b < chunks) {
-        const int nb = b + (int)gridDim.x;
-        if (nb < chunks) {
-            where(nb, nti, nbeg, nfull);
-            if (nfull) load(nti, nbeg, nxt);
-        }
-        const yolo_sgd_tensor &t = tab.t[ti];
-        if (full) {
-#pragma unroll
-            for (int u = 0; u < 2; ++u) {
-                const long i = beg + (long)(u * 1024 + threadIdx.x) * 4;
-                sgd4<MODE>(cur.p[u], cur.g[u], cur.b[u], clip, a);
-                *reinterpret_cast<float4 *>(t.p + i) = cur.p[u];
-                if (MODE != MOM_NONE) *reinterpret_cast<float4 *>(t.buf + i) = cur.b[u];
-                if (t.p_bf16) *reinterpret_cast<uint2 *>((bf16_t *)t.p_bf16 + i) = pack_bf16x4(cur.p[u]);
-            }
-        } else {
-            sgd_scalar<MODE>(t, beg + threadIdx.x, min(t.n, beg + MT_CHUNK), 1024, clip, a);     // last, partial chunk of a tensor
-        }
-        b = nb; ti = nti; beg = nbeg; full = nfull;
-        cur = nxt;
-    }
+    if (mt_skipped(a.skip_flag)) return;
+    mt_walk_bg(tab, chunks, SgdOp<MODE>{clip_coefficient(a.norm_sq, a.max_norm), a});
 }
 
 }  // namespace yolo
@@ -195,35 +127,16 @@ static int sgd_tensor_ok(const char *who, const yolo_sgd_tensor &e, int idx, int
     return 0;
 }
 
-// every tensor of the call is checked before the first launch: a refused call launches nothing
 static int sgd_foreground(const char *who, const yolo_sgd_tensor *t, int count, const SgdArgs &a, int mode, yolo_stream_t stream)
 {
-    for (int i = 0; i < count; ++i) {
-        if (int rc = sgd_tensor_ok(who, t[i], i, mode)) return rc;
-        if ((t[i].n + MT_CHUNK - 1) / MT_CHUNK > 0x7fffffffL) return fail(YOLO_E_UNSUPPORTED, "%s: tensor %d is too large", who, i);
-    }
-    for (int base = 0; base < count;) {
-        SgdTable tab{};
-        long chunks = 0;
-        int k = 0;
-        for (; base + k < count && k < YOLO_MT_MAX; ++k) {
-            const long c = (t[base + k].n + MT_CHUNK - 1) / MT_CHUNK;
-            if (chunks + c > 0x7fffffffL) break;
-            tab.t[k] = t[base + k]; tab.first[k] = (int)chunks;
-            chunks += c;
-        }
-        tab.first[k] = (int)chunks;
-        tab.count = k;
-        if (chunks > 0) {
-            const dim3 grid((unsigned)chunks), block(256);
-            if (mode == MOM_NONE) hipLaunchKernelGGL(sgd_multi_kernel<MOM_NONE>, grid, block, 0, STRM(stream), tab, a);
-            else if (mode == MOM_FIRST) hipLaunchKernelGGL(sgd_multi_kernel<MOM_FIRST>, grid, block, 0, STRM(stream), tab, a);
-            else hipLaunchKernelGGL(sgd_multi_kernel<MOM_NEXT>, grid, block, 0, STRM(stream), tab, a);
-            if (int rc = check_launch(who)) return rc;
-        }
-        base += k;
-    }
-    return 0;
+    auto ok = [&](const char *w, const yolo_sgd_tensor &e, int idx) { return sgd_tensor_ok(w, e, idx, mode); };
+    return mt_foreground<MT_CHUNK>(who, t, count, ok, [&](const MtTable<yolo_sgd_tensor> &tab, long chunks) {
+        const dim3 grid((unsigned)chunks), block(256);
+        if (mode == MOM_NONE) hipLaunchKernelGGL(sgd_multi_kernel<MOM_NONE>, grid, block, 0, STRM(stream), tab, a);
+        else if (mode == MOM_FIRST) hipLaunchKernelGGL(sgd_multi_kernel<MOM_FIRST>, grid, block, 0, STRM(stream), tab, a);
+        else hipLaunchKernelGGL(sgd_multi_kernel<MOM_NEXT>, grid, block, 0, STRM(stream), tab, a);
+        return check_launch(who);
+    });
 }
 
 YOLO_API int yolo_sgd_step(float *p, const float *g, float *buf, long n, float lr, float momentum, float dampening, float weight_decay, int nesterov,
@@ -250,37 +163,19 @@ YOLO_API int yolo_sgd_step_multi_bg(const yolo_sgd_tensor *t, int count, float l
                                     int first_step, const double *norm_sq, float max_norm, const float *skip_flag, int workgroups, yolo_stream_t stream)
 {
     const char *who = "yolo_sgd_step_multi_bg";
-    if (!t || count < 0 || count > YOLO_MT_MAX || workgroups < 1 || workgroups > 256)
-        return fail(YOLO_E_ARG, "%s: bad argument (at most %d tensors, 1 .. 256 workgroups)", who, YOLO_MT_MAX);
     SgdArgs a;
     int mode;
     if (int rc = sgd_args(who, lr, momentum, dampening, weight_decay, nesterov, first_step, norm_sq, max_norm, skip_flag, a, mode)) return rc;
-    SgdTable tab{};
-    long chunks = 0;
-    for (int k = 0; k < count; ++k) {
-        if (int rc = sgd_tensor_ok(who, t[k], k, mode)) return rc;
-        tab.t[k] = t[k]; tab.first[k] = (int)chunks;
-        chunks += (t[k].n + MT_CHUNK - 1) / MT_CHUNK;
-        if (chunks > 0x7fffffffL) return fail(YOLO_E_UNSUPPORTED, "%s: too many elements", who);
-    }
-    tab.first[count] = (int)chunks;
-    tab.count = count;
-    if (chunks == 0) return 0;
-    constexpr int BG_LDS = 96 * 1024;       // with 1024 threads: one such workgroup per CU, and no 128-KB conv workgroup beside it
     const void *fn = mode == MOM_NONE ? (const void *)sgd_multi_bg_kernel<MOM_NONE>
                    : mode == MOM_FIRST ? (const void *)sgd_multi_bg_kernel<MOM_FIRST> : (const void *)sgd_multi_bg_kernel<MOM_NEXT>;
-    static bool attr_done[3][64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_done[mode][dev]) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, BG_LDS);
-        if (e != hipSuccess) return fail((int)e, "%s: hipFuncSetAttribute(%d B LDS): %s", who, BG_LDS, hipGetErrorString(e));
-        attr_done[mode][dev] = true;
-    }
-    const dim3 grid((unsigned)std::min<long>(workgroups, chunks)), block(1024);
-    const int nchunks = (int)chunks;
-    if (mode == MOM_NONE) hipLaunchKernelGGL(sgd_multi_bg_kernel<MOM_NONE>, grid, block, BG_LDS, STRM(stream), tab, nchunks, a);
-    else if (mode == MOM_FIRST) hipLaunchKernelGGL(sgd_multi_bg_kernel<MOM_FIRST>, grid, block, BG_LDS, STRM(stream), tab, nchunks, a);
-    else hipLaunchKernelGGL(sgd_multi_bg_kernel<MOM_NEXT>, grid, block, BG_LDS, STRM(stream), tab, nchunks, a);
+    static bool lds_done[3][64] = {};
+    auto ok = [&](const char *w, const yolo_sgd_tensor &e, int idx) { return sgd_tensor_ok(w, e, idx, mode); };
+    MtBackground<yolo_sgd_tensor> bg;
+    if (int rc = mt_background(who, t, count, workgroups, true, ok, fn, lds_done[mode], bg)) return rc;
+    if (bg.grid == 0) return 0;
+    const dim3 grid(bg.grid), block(1024);
+    if (mode == MOM_NONE) hipLaunchKernelGGL(sgd_multi_bg_kernel<MOM_NONE>, grid, block, BG_LDS, STRM(stream), bg.tab, bg.chunks, a);
+    else if (mode == MOM_FIRST) hipLaunchKernelGGL(sgd_multi_bg_kernel<MOM_FIRST>, grid, block, BG_LDS, STRM(stream), bg.tab, bg.chunks, a);
+    else hipLaunchKernelGGL(sgd_multi_bg_kernel<MOM_NEXT>, grid, block, BG_LDS, STRM(stream), bg.tab, bg.chunks, a);
     return check_launch(who);
 }

@@ -71,6 +71,9 @@ class PoolDesc(ctypes.Structure):
                 ("in_halo", ctypes.c_int32), ("out_halo", ctypes.c_int32)]
 
 
+MT_MAX = 48                  # YOLO_MT_MAX: tensors per multi-tensor launch, and all a background entry takes
+
+
 class AdamTensor(ctypes.Structure):
     """struct yolo_adam_tensor (include/yolo_hip.h)."""
 

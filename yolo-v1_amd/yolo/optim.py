@@ -17,9 +17,10 @@ import torch
 
 import ctypes
 import os
+import weakref
 
 from . import _hip
-from ._hip import AccumTensor, AdamTensor, EmaTensor, SgdTensor, check, lib, ptr, stream
+from ._hip import MT_MAX, AccumTensor, AdamTensor, EmaTensor, SgdTensor, check, lib, ptr, stream
 from .config import CONFIG as CFG
 
 
@@ -30,6 +31,22 @@ BG_CUS = 128       # CUs the background update of the Linear layers holds (yolo_
                    # kernels: 64 was the optimum and 96 no better.)
 EMA_BACKGROUND = True   # ModelEMA averages the parameters of a background update in the background too ("Weight EMA", has the step times)
 OVERLAP = os.environ.get("YOLO_ADAM_OVERLAP", "1") != "0"     # attach_plan(overlap=True) takes effect (switch for A/B runs)
+
+
+def _wait_before_state_io(waiter, module) -> None:
+    """``module.state_dict()`` and ``module.load_state_dict()`` first make the current stream wait for ``waiter``'s background launch
+    (``waiter.synchronize()``).  Once per module (``waiter._hooked``); the hooks hold the waiter weakly."""
+    if id(module) in waiter._hooked:
+        return
+    waiter._hooked.add(id(module))
+    me = weakref.ref(waiter)
+
+    def wait(*_a, **_k):
+        w = me()
+        if w is not None:
+            w.synchronize()
+    module.register_state_dict_pre_hook(wait)
+    module.register_load_state_dict_pre_hook(wait)
 
 
 def _f32c(g: torch.Tensor) -> torch.Tensor:
@@ -196,7 +213,7 @@ class _Fused(torch.optim.Optimizer):
             for (key, late), items in sorted(by_key.items(), key=lambda kv: kv[0][1]):      # the foreground launch first
                 tab = (type(items[0][1]) * len(items))(*[it[1] for it in items])
                 side = None
-                if late and len(items) <= 48:
+                if late and len(items) <= MT_MAX:
                     side = self._side_stream()
                     if not side_used:
                         side.wait_stream(main_t)             # behind the gradients, the norm and the last forward's / backward's reads
@@ -241,18 +258,8 @@ class _Fused(torch.optim.Optimizer):
         bulk: ``state_dict()`` (checkpoints, ``torch.save(model.state_dict())``), ``load_state_dict()`` (resume) and
         ``copy.deepcopy`` (EMA copies; models.YOLOv1.__deepcopy__ asks the plan) -- no caller has to know about the second stream."""
         owner = plan.owner() if getattr(plan, "owner", None) is not None else None
-        if owner is None or id(owner) in self._hooked:
-            return
-        self._hooked.add(id(owner))
-        import weakref
-        me = weakref.ref(self)
-
-        def wait(*_a, **_k):
-            opt = me()
-            if opt is not None:
-                opt.synchronize()
-        owner.register_state_dict_pre_hook(wait)
-        owner.register_load_state_dict_pre_hook(wait)
+        if owner is not None:
+            _wait_before_state_io(self, owner)
 
     def state_dict(self):
         self.synchronize()
@@ -368,7 +375,7 @@ class SGD(_Fused):
 
     def _step_on_cpu(self, all_params):
         """CPU parameters: the same step in stock torch ops -- the clip coefficient formed in fp32 as the kernels form it
-        (sgd_begin in sgd.hip, which is clip_grad_norm_'s), then torch.optim.SGD's own sequence of operations."""
+        (clip_coefficient in csrc/multi_tensor.h, which is clip_grad_norm_'s), then torch.optim.SGD's own sequence of operations."""
         known = self._known_norms()
         clip = None
         if self.max_grad_norm is not None:
@@ -464,25 +471,10 @@ class ModelEMA:
         self.background = EMA_BACKGROUND if background is None else bool(background)
         self.module = copy.deepcopy(model).eval()       # waits for a background update of ``model`` (models._PlanOwner.__deepcopy__)
         self.module.requires_grad_(False)
-        import weakref
         self._model = weakref.ref(model)
         self._event, self._event_device = None, None    # behind the last background launch
         self._hooked: set = set()
-        self._hook(self.module)
-
-    def _hook(self, mod) -> None:
-        if id(mod) in self._hooked:
-            return
-        self._hooked.add(id(mod))
-        import weakref
-        me = weakref.ref(self)
-
-        def wait(*_a, **_k):
-            ema = me()
-            if ema is not None:
-                ema.synchronize()
-        mod.register_state_dict_pre_hook(wait)
-        mod.register_load_state_dict_pre_hook(wait)
+        _wait_before_state_io(self, self.module)
 
     def effective_decay(self, updates: int | None = None) -> float:
         """the decay of update number ``updates`` (default: the last one made): the warm-up of ``tau`` lets the first updates follow the model"""
@@ -535,7 +527,7 @@ class ModelEMA:
             torch._foreach_lerp_(cpu_e, cpu_p, w)
         if not (fore or back):
             return
-        if len(back) > 48:                              # more than one background table: the optimizer took the foreground as well
+        if len(back) > MT_MAX:                            # more than one background table: the optimizer took the foreground as well
             fore, back = fore + back, []
         if not back and hasattr(opt, "synchronize"):
             opt.synchronize()                           # everything in the foreground: the optimizer's background launch writes p, wait for it
@@ -545,7 +537,7 @@ class ModelEMA:
             if fore:
                 self.synchronize()                      # these may include tensors an earlier update left to the second stream (long done by now)
                 tab = (EmaTensor * len(fore))(*[EmaTensor(e.data_ptr(), p.data_ptr(), e.numel()) for e, p in fore])
-                check(lib().yolo_ema_update_multi(tab, len(fore), w, ptr(skip), stream()), "yolo_ema_update_multi")   # one launch per 48 tensors
+                check(lib().yolo_ema_update_multi(tab, len(fore), w, ptr(skip), stream()), "yolo_ema_update_multi")   # one launch per MT_MAX tensors
             if back:
                 # The second stream runs its launches in order.  The optimizer's background launch of this step is already on it, so the
                 # EMA reads the updated p; the NEXT step's background launch -- the only writer of these p -- will be enqueued on the same
@@ -577,7 +569,7 @@ class ModelEMA:
             if owner is None or id(owner) not in names:
                 continue
             twin = self.module.get_submodule(names[id(owner)])
-            self._hook(twin)
+            _wait_before_state_io(self, twin)
             twin_plan = twin.__dict__.get("_plan")
             if twin_plan is not None and hasattr(twin_plan, "params_ready"):
                 twin_plan.params_ready.event = ev
@@ -716,7 +708,7 @@ class GradAccumulator:
             else:
                 tab = (AccumTensor * len(items))(*[AccumTensor(d.data_ptr(), x.data_ptr(), y.data_ptr() if y is not None else None, d.numel())
                                                    for d, x, y in items])
-                check(lib().yolo_grad_accum_multi(tab, len(items), self.alpha, None, stream()), "yolo_grad_accum_multi")   # one launch per 48 tensors
+                check(lib().yolo_grad_accum_multi(tab, len(items), self.alpha, None, stream()), "yolo_grad_accum_multi")   # one launch per MT_MAX tensors
 
     def _hook(self, k: int):
         def fold(lo: int, hi: int):
