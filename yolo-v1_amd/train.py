@@ -7,7 +7,9 @@
 Defaults follow src/train.py:269-338: batch 64, lr 1e-4, weight decay 5e-4, LR decay x0.1 at epochs
 75 and 105, lambda_coord 5, lambda_noobj 0.5.  ``--backbone`` is additive (the reference hard-codes
 ResNet50, which needs torchvision); ``--synthetic N`` trains on N random images instead of PASCAL VOC;
-``--backbone yolov1 --backbone-weights PATH`` starts from a trunk that pretrain.py trained as a classifier (the paper's first stage).
+``--backbone yolov1 --backbone-weights PATH`` starts from a trunk that pretrain.py trained as a classifier (the paper's first stage);
+``--init kaiming`` gives what that file does not hold (or, without one, the whole network) He initialisation -- the default, the
+reference's, does not train the 24-layer network from scratch (``yolo.models.init_kaiming_``).
 """
 
 from __future__ import annotations
@@ -82,6 +84,13 @@ def main():
                     help="--backbone yolov1 only: a classification checkpoint of pretrain.py whose trunk (features.N.*) initialises the backbone "
                          "(YOLOv1Backbone.load_pretrained); --resume wins over it.  Default: random initialisation")
     ap.add_argument("--use-ema", action="store_true", help="with --backbone-weights: take the checkpoint's averaged weights (ema_state_dict) when it has them")
+    ap.add_argument("--init", choices=["default", "kaiming"], default="default",
+                    help="default: PyTorch's Conv2d / Linear initialisation, the reference's -- with --backbone yolov1 it does NOT train the 24-layer "
+                         "network from scratch (no normalisation layers: the input-dependent part of the activations shrinks by ~0.4 per layer, to "
+                         "~1e-8 of the first layer's behind the 20th convolution; the 20-layer classifier stays at ln 4 = 1.3863 over 30 SGD steps "
+                         "where He initialisation goes 1.4510 -> 0.6878).  kaiming: He initialisation for LeakyReLU(0.1) with zero biases, the output "
+                         "layer as it is (yolo.models.init_kaiming_); applied before --backbone-weights, which then overwrites the 40 trunk tensors "
+                         "(the four detection convolutions and FC1 keep it); --backbone resnet50: the head only.  --resume wins over it")
     ap.add_argument("--seed", type=int, default=None, help="seed of torch, numpy, random and the loaders (every epoch starts from (seed, epoch))")
     a = ap.parse_args()
     if a.accum_steps < 1:
@@ -135,14 +144,18 @@ def main():
                             worker_init_fn=worker_init)
 
     backbone = YOLOv1Backbone() if a.backbone == "yolov1" else ResNetBackbone(pretrained=not a.no_pretrained, freeze=a.freeze_backbone)
-    if a.backbone_weights and not a.resume:
+    model = YOLOv1(backbone=backbone, num_classes=20, S=7, B=2)
+    if a.init == "kaiming" and not a.resume:
+        from yolo.models import init_kaiming_
+        init_kaiming_(model if a.backbone == "yolov1" else model.head)
+    if a.backbone_weights and not a.resume:          # behind --init: the checkpoint's 40 trunk tensors replace whatever the trunk was given
         ck0 = torch.load(a.backbone_weights, map_location="cpu", weights_only=True)
         sd = ck0["ema_state_dict"] if (a.use_ema and "ema_state_dict" in ck0) else ck0["model_state_dict"]
         loaded = backbone.load_pretrained(sd)
         if rank == 0:
             print(f"backbone: loaded {loaded} tensors from {a.backbone_weights}" + (" (averaged weights)" if sd is not ck0["model_state_dict"] else ""))
         del ck0, sd
-    model = YOLOv1(backbone=backbone, num_classes=20, S=7, B=2).to(device)
+    model = model.to(device)
     if world > 1:
         broadcast_parameters(model)
     criterion = YOLOLoss(S=7, B=2, C=20, lambda_coord=a.lambda_coord, lambda_noobj=a.lambda_noobj)
@@ -175,6 +188,7 @@ def main():
         if "scheduler_state_dict" in ck:
             scheduler.load_state_dict(ck["scheduler_state_dict"])
         start_epoch = ck["epoch"] + 1
+        a.init = ck.get("init", "default")          # --resume wins over --init: the weights are the file's, and so is the record of how they began
         best_val, best_map = ck.get("val_loss"), ck.get("mAP50:95")
     ema = None
     if a.ema_decay is not None:
@@ -193,6 +207,8 @@ def main():
         extra["accum_steps"] = a.accum_steps
     if a.augment != "reference":          # (the default: the checkpoint's keys are those of a run without the option)
         record = {**(record or {}), "augment": a.augment}
+    if a.init != "default":               # (likewise)
+        record = {**(record or {}), "init": a.init}
     res = training.train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, a.epochs, ckdir,
                          save_frequency=a.save_frequency, compute_map=a.compute_map, start_epoch=start_epoch,
                          best_val_loss_init=best_val, best_map_init=best_map, seed=a.seed, record=record, ema=ema, **extra)

@@ -8,7 +8,8 @@ operations in the sampled order -> ToTensor -> Normalize, into the stem's NHWC4 
 tensor (``U8Batch.to_tensor``).  The result is bit-identical to the host path (``_Augment.apply`` + ``_Preprocess``) for the
 same parameters: tests/test_gpu_augment.py.  The Darknet recipe (``_DarknetAugment``: ``JitterParams`` entries) goes through the same two
 launches -- window with edge replication, flip, one HSV operation -- and may share a batch with ``AugParams`` entries:
-tests/test_gpu_darknet_augment.py.
+tests/test_gpu_darknet_augment.py.  The classification pretraining (``dataset._ClassifyTransform``) sends ``AugParams`` with its ``flip``
+set, into ``YOLOv1Classifier``'s trunk plan: tests/test_gpu_pretrain_scale.py.
 
     ds = create_voc_datasets(..., device_transform=True)
     loader = DataLoader(ds, batch_size=64, collate_fn=collate_u8, pin_memory=True)
@@ -151,6 +152,7 @@ class U8Batch:
                     d.n_ops, d.ops[0] = 1, _hip.AUG_HSV
                     d.brightness, d.saturation, d.hue_shift = p.exposure, p.saturation, int(p.hue * 255)
                     continue
+                d.flags = _hip.AUG_F_FLIP if p.flip else 0          # (the classification transform's; the kernel mirrors the columns of stage 1)
                 d.n_ops = len(p.ops)
                 for i, op in enumerate(p.ops):
                     d.ops[i] = op

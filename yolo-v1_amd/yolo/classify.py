@@ -226,7 +226,8 @@ class YOLOv1Classifier(_PlanOwner, nn.Module):
     ``features.N.*``), a global average pool and ``Linear(1024, num_classes)``.  (N, 3, H, W) -> (N, num_classes) logits; H and W are
     free (224 in the paper).
 
-    Device tensors: two engine plans -- the conv / pool trunk and [Flatten, Linear] -- with the ``GlobalAvgPool`` node between them."""
+    Device tensors: two engine plans -- the conv / pool trunk and [Flatten, Linear] -- with the ``GlobalAvgPool`` node between them;
+    ``hip_plans()`` lists them in forward order, which is how ``parallel.make_grad_reducer`` and ``yolo.optim.GradAccumulator`` find them."""
 
     def __init__(self, num_classes: int = 1000):
         super().__init__()
@@ -253,7 +254,11 @@ class YOLOv1Classifier(_PlanOwner, nn.Module):
         return [self.trunk_plan(), self.head_plan()]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
+        """x: (N, 3, H, W) fp32 images, or a ``yolo.augment.U8Batch`` (decoded uint8 images + crop / colour / flip parameters): on the device
+        it is augmented straight into the trunk plan's stem input buffer, as ``YOLOv1.forward`` does; on the CPU its fp32 tensor is taken"""
         if x.is_cuda:
             f = engine.run_plan(self.trunk_plan(), x, self.training)
             return engine.run_plan(self.head_plan(), self.pool(f), self.training)
+        if not isinstance(x, torch.Tensor):
+            x = x.to_tensor()
         return self.fc(self._flatten(self.pool(self.features(x))))

@@ -95,10 +95,7 @@ def parse_voc_xml(node: ET.Element) -> dict:
 OP_BRIGHTNESS, OP_SATURATION, OP_HUE, OP_HSV = 0, 1, 2, 4      # = YOLO_AUG_* of include/yolo_hip.h (3 is not assigned)
 
 
-class AugParams(NamedTuple):
-    """What ``_Augment.sample`` draws for one image: the crop, the colour operations in the order they are applied, their factors
-    (``hue`` is the fraction of the hue circle; the H byte moves by ``int(hue * 255)``).  The host path (``_Augment.apply``) and
-    the device path (yolo/augment.py -> yolo_augment_u8) both take it."""
+class _AugFields(NamedTuple):
     top: int
     left: int
     ch: int
@@ -109,13 +106,51 @@ class AugParams(NamedTuple):
     hue: float = 0.0
 
 
+class AugParams(_AugFields):
+    """What ``_Augment.sample`` draws for one image: the crop, the colour operations in the order they are applied, their factors
+    (``hue`` is the fraction of the hue circle; the H byte moves by ``int(hue * 255)``).  The host path (``_Augment.apply``) and
+    the device path (yolo/augment.py -> yolo_augment_u8) both take it.
+
+    ``flip`` (last argument, default False): the output is mirrored left to right.  ``_Augment.sample`` never draws one; the classification
+    transform (``_ClassifyTransform.sample``) does.  It is an attribute beside the eight tuple entries, not a ninth: the tuple -- what
+    iteration, ``len`` and ``tuple(p)`` give -- stays the crop and the colour parameters; ``==``, ``hash``, ``repr``, ``_replace`` and
+    pickling carry the flip along.  The colour operations are per-pixel, so mirroring behind them (the host path) and in front of them
+    (the kernel) give the same bytes."""
+    flip = False
+
+    def __new__(cls, top, left, ch, cw, ops=(), brightness=1.0, saturation=1.0, hue=0.0, flip=False):
+        self = super().__new__(cls, top, left, ch, cw, ops, brightness, saturation, hue)
+        if flip:
+            self.flip = True          # (kept in the instance's __dict__, which is also what pickle ships as its state)
+        return self
+
+    def _replace(self, **kwargs):
+        flip = kwargs.pop("flip", self.flip)
+        return AugParams(*super()._replace(**kwargs), flip=flip)
+
+    def __eq__(self, other):
+        same = tuple.__eq__(self, other)
+        return same if same is NotImplemented else (same and self.flip == getattr(other, "flip", False))
+
+    def __ne__(self, other):
+        return not self == other
+
+    def __hash__(self):
+        return hash((tuple(self), self.flip))
+
+    def __repr__(self):
+        return super().__repr__()[:-1] + f", flip={self.flip})"
+
+
 def crop_boxes(boxes, p: AugParams, size) -> List[List[float]]:
-    """pixel-space XYXY boxes shifted into the crop, clamped to it and scaled with it to ``size`` = (H, W)"""
+    """pixel-space XYXY boxes shifted into the crop, clamped to it and scaled with it to ``size`` = (H, W) (and mirrored with ``p.flip``)"""
     sx, sy = size[1] / p.cw, size[0] / p.ch
     out = []
     for x0, y0, x1, y1 in boxes:
         x0, x1 = min(max(x0 - p.left, 0.0), p.cw) * sx, min(max(x1 - p.left, 0.0), p.cw) * sx
         y0, y1 = min(max(y0 - p.top, 0.0), p.ch) * sy, min(max(y1 - p.top, 0.0), p.ch) * sy
+        if p.flip:
+            x0, x1 = size[1] - x1, size[1] - x0
         out.append([x0, y0, x1, y1])
     return out
 
@@ -211,7 +246,7 @@ class _Augment:
         return AugParams(top, left, ch, cw, order, b, s, hu)
 
     def apply(self, image: Image.Image, boxes: List[List[float]], p: AugParams):
-        """The host path: crop, PIL bilinear resize and the colour operations of ``p`` in its order; boxes go with the crop."""
+        """The host path: crop, PIL bilinear resize, the colour operations of ``p`` in its order and its flip; boxes go with the crop."""
         image = image.crop((p.left, p.top, p.left + p.cw, p.top + p.ch)).resize((self.size[1], self.size[0]), Image.BILINEAR)
         for op in p.ops:
             if op == OP_BRIGHTNESS:
@@ -220,6 +255,8 @@ class _Augment:
                 image = ImageEnhance.Color(image).enhance(p.saturation)
             else:
                 image = self._hue(image, p.hue)
+        if p.flip:
+            image = image.transpose(Image.FLIP_LEFT_RIGHT)
         return image, crop_boxes(boxes, p, self.size)
 
     def __call__(self, image: Image.Image, boxes: List[List[float]]):
@@ -468,7 +505,9 @@ IMAGE_EXTENSIONS = (".jpg", ".jpeg", ".png", ".bmp", ".ppm", ".webp")
 
 class _ClassifyTransform:
     """PIL image -> normalised (3, size, size) tensor.  Training: the geometry and colour of ``_Augment`` (no boxes) and a horizontal flip with
-    probability 1/2, all drawn from torch's global generator; validation: the Resize of ``inference._Preprocess``."""
+    probability 1/2, all drawn from torch's global generator; validation: the Resize of ``inference._Preprocess``.  Split like ``_Augment``:
+    ``sample`` draws an ``AugParams`` (the flip in its ``flip`` field), ``apply`` is the host path, and the device path
+    (``device_transform=True`` datasets -> ``yolo.augment.collate_u8`` -> yolo_augment_u8) takes the same parameters."""
 
     def __init__(self, size: int, train: bool):
         from .inference import _Preprocess
@@ -476,20 +515,37 @@ class _ClassifyTransform:
         self.augment = _Augment((size, size)) if train else None
         self.finish = _Preprocess(size=(size, size))          # Resize (a no-op behind the crop) + ToTensor + Normalize
 
-    def __call__(self, image: Image.Image) -> torch.Tensor:
+    def sample(self, w: int, h: int) -> AugParams:
+        """training: ``_Augment.sample`` and then one ``rand`` for the flip; validation: the whole image, no operation, nothing drawn"""
+        if not self.train:
+            return AugParams(0, 0, h, w)
+        p = self.augment.sample(w, h)
+        return p._replace(flip=float(torch.rand(1).item()) < 0.5)
+
+    def apply(self, image: Image.Image, p: AugParams) -> torch.Tensor:
         if self.train:
-            image, _ = self.augment(image, [])
-            if float(torch.rand(1).item()) < 0.5:
-                image = image.transpose(Image.FLIP_LEFT_RIGHT)
+            image, _ = self.augment.apply(image, [], p)
         return self.finish(image)
+
+    def __call__(self, image: Image.Image) -> torch.Tensor:
+        return self.apply(image, self.sample(*image.size))
+
+
+def _u8_sample(transform: _ClassifyTransform, image: Image.Image, label: int):
+    """a ``device_transform`` sample for ``yolo.augment.collate_u8``: (decoded uint8 HWC tensor, AugParams, label tensor)"""
+    return torch.from_numpy(np.asarray(image, dtype=np.uint8).copy()), transform.sample(*image.size), torch.tensor(label, dtype=torch.int64)
 
 
 class ImageFolderClassification(Dataset):
     """``<root>/<split>/<class>/*`` image folders: the classes are the sorted directory names of the split, a sample is
     (normalised (3, size, size) tensor, class index).  Pillow only.  ``classes``: the class list of another split (the validation split of a
-    training run uses the training split's indices; a directory it does not name is an error)."""
+    training run uses the training split's indices; a directory it does not name is an error).  ``device_transform=True``: a sample is
+    (decoded uint8 HWC tensor, AugParams, label tensor) for ``yolo.augment.collate_u8(samples, size=(size, size))`` -- crop, resize, colour
+    jitter, flip and normalisation then run on the device with the very parameters drawn here."""
 
-    def __init__(self, root: str | Path, split: str = "train", size: int = 224, train: bool | None = None, classes: List[str] | None = None):
+    def __init__(self, root: str | Path, split: str = "train", size: int = 224, train: bool | None = None, classes: List[str] | None = None,
+                 device_transform: bool = False):
+        self.device_transform = device_transform
         self.dir = Path(root) / split
         if not self.dir.is_dir():
             raise FileNotFoundError(f"no directory {self.dir}: expected <root>/{split}/<class>/<image files>")
@@ -512,15 +568,21 @@ class ImageFolderClassification(Dataset):
 
     def __getitem__(self, idx: int):
         path, label = self.samples[idx]
-        return self.transform(Image.open(path).convert("RGB")), label
+        image = Image.open(path).convert("RGB")
+        if self.device_transform:
+            return _u8_sample(self.transform, image, label)
+        return self.transform(image), label
 
 
 class SyntheticClassificationDataset(Dataset):
     """``length`` images of ``num_classes`` learnable classes without a dataset on disk: sample ``idx`` has class ``idx % num_classes``, and an image is
     its class's fixed low-resolution colour pattern (8 x 8 blocks, drawn once from ``seed``) plus per-sample noise (from ``(seed, idx)``), as
-    uint8 RGB through the same Pillow transforms as the folder dataset."""
+    uint8 RGB through the same Pillow transforms as the folder dataset -- or, with ``device_transform=True``, as the folder dataset's
+    (uint8 HWC tensor, AugParams, label tensor) samples."""
 
-    def __init__(self, length: int = 256, num_classes: int = 10, size: int = 224, seed: int = 0, train: bool = False, noise: float = 24.0):
+    def __init__(self, length: int = 256, num_classes: int = 10, size: int = 224, seed: int = 0, train: bool = False, noise: float = 24.0,
+                 device_transform: bool = False):
+        self.device_transform = device_transform
         self.length, self.num_classes, self.size, self.seed, self.noise = length, num_classes, size, seed, noise
         rng = np.random.Generator(np.random.PCG64([seed, 1 << 20]))
         self.patterns = rng.integers(32, 224, (num_classes, 8, 8, 3)).astype(np.float32)
@@ -537,4 +599,6 @@ class SyntheticClassificationDataset(Dataset):
         return Image.fromarray(np.clip(arr, 0, 255).astype(np.uint8), "RGB")
 
     def __getitem__(self, idx: int):
+        if self.device_transform:
+            return _u8_sample(self.transform, self.image(idx), idx % self.num_classes)
         return self.transform(self.image(idx)), idx % self.num_classes

@@ -48,6 +48,30 @@ class _PlanOwner:
         return new
 
 
+@torch.no_grad()
+def init_kaiming_(module: nn.Module) -> int:
+    """He initialisation for the LeakyReLU(0.1) stacks of this file, in place: every ``nn.Conv2d`` and every ``nn.Linear`` of ``module`` gets
+    ``kaiming_normal_(a=0.1, mode="fan_in", nonlinearity="leaky_relu")`` and a zero bias -- except the module's LAST Linear (the logits, the
+    detection output), which keeps what it has: nothing follows it, so its scale does not compound.  The draws come from torch's global
+    generator in ``module.modules()`` order.  Returns the number of tensors written.
+
+    Why: PyTorch's default (``kaiming_uniform_(a=sqrt(5))``, the reference's initialisation) scales the signal by about 0.4 per
+    conv + LeakyReLU(0.1) layer, and these networks have no normalisation layers: behind 20 layers the input-dependent part of the activations
+    is ~1e-8 of the first layer's, far below the bf16 resolution of the bias term it rides on, and nothing is learnt (DESIGN.md,
+    "Classification pretraining").  Extension of the reference surface; call it before the model moves to its device."""
+    linears = [m for m in module.modules() if isinstance(m, nn.Linear)]
+    last = linears[-1] if linears else None
+    written = 0
+    for m in module.modules():
+        if isinstance(m, (nn.Conv2d, nn.Linear)) and m is not last:
+            nn.init.kaiming_normal_(m.weight, a=0.1, mode="fan_in", nonlinearity="leaky_relu")
+            written += 1
+            if m.bias is not None:
+                nn.init.zeros_(m.bias)
+                written += 1
+    return written
+
+
 class Backbone(nn.Module):
     """Abstract feature extractor: subclasses map (N,3,H,W) images to (N,C,H',W') features."""
 

@@ -603,7 +603,9 @@ class GradAccumulator:
 
         g = (g_1 + ... + g_K) / K          as the chain  a = alpha g_1;  a = fmaf(alpha, g_k, a);  g = fmaf(alpha, g_K, a),   alpha = fp32(1 / K)
 
-    -- the gradient of the concatenated batch, because YOLOLoss divides by the local N and the micro-batches are equal.  The last link
+    -- the gradient of the concatenated batch, because YOLOLoss divides by the local N and the micro-batches are equal (and so does
+    ``yolo.classify.SoftmaxCrossEntropy``, the mean over its batch: with equal micro-batches and equal shards the folded, rank-averaged
+    gradient of the classifier is the concatenated batch's too).  The last link
     folds the accumulator INTO THE GRADIENT MEMORY, not the other way round: ``p.grad`` stays the arena view (or autograd's tensor), so the
     optimizers, the clip norm, the bf16 shadows, the background update of the Linear layers and the reducers read what they read without
     accumulation, and none of them changes.
@@ -620,7 +622,9 @@ class GradAccumulator:
 
     On a GPU, a fused YOLOv1 (``model._fusable()``) or a ``DetectionHead`` with ``hip_plan`` gets the plan's gradient arena attached if it has
     none (the plan's ``on_*`` callbacks stay None without a reducer) and ONE flat accumulator of the arena's size: the whole network is one
-    yolo_grad_accum call per micro-batch (accum.hip; 8 B per element for the first, 12 B for the others).  Parameters outside a plan (a ResNet
+    yolo_grad_accum call per micro-batch (accum.hip; 8 B per element for the first, 12 B for the others).  A model that runs several plans and
+    lists them as ``hip_plans()`` (``YOLOv1Classifier``: trunk, head) gets an arena and an accumulator per plan, and the arenas go through
+    yolo_grad_accum_multi as one launch.  Parameters outside a plan (a ResNet
     trunk, custom modules) get an accumulator each and go through yolo_grad_accum_multi.  CPU tensors take stock torch ops
     (``torch._foreach_mul_`` / ``torch._foreach_add_`` with alpha).  ``steps == 1`` allocates nothing and launches nothing.
 
@@ -664,7 +668,8 @@ class GradAccumulator:
             head = getattr(model, "head", None)
             plan = model.hip_plan() if (hasattr(model, "_fusable") and model._fusable()) else \
                 head.hip_plan() if (head is not None and hasattr(head, "hip_plan")) else None
-            if plan is not None:
+            own = [plan] if plan is not None else list(model.hip_plans()) if hasattr(model, "hip_plans") else []
+            for plan in own:
                 if plan.arena is None:
                     plan.attach_grad_arena(params[0].device)
                 plans.setdefault(id(plan), (plan, None))

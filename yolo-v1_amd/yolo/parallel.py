@@ -185,6 +185,9 @@ def make_grad_reducer(model: torch.nn.Module, device, group=None):
       ``OverlappedGradAllReduce`` (all-reduce of finished layers while backward continues, FC1's 822 MB first);
     * ``DetectionHead`` on a ResNet trunk on a GPU: the head's plan overlapped, the trunk's parameters (which autograd
       hands over after the head) with ``GradAllReduce``;
+    * a model that runs several plans and lists them as ``hip_plans()`` (``YOLOv1Classifier``: trunk, head) on a GPU: one
+      ``OverlappedGradAllReduce`` per plan, in the order backward runs them -- the reverse of the forward order ``hip_plans()`` gives, head
+      first -- so every rank enqueues its collectives in the same order; parameters outside every plan with ``GradAllReduce``;
     * anything else (CPU tensors, custom modules): ``GradAllReduce`` over all parameters.
 
     The arena path OVERWRITES gradients every backward, which is what the reference's loop does (zero_grad before every backward,
@@ -198,4 +201,10 @@ def make_grad_reducer(model: torch.nn.Module, device, group=None):
         head_ids = {id(p) for p in head.parameters()}
         rest = [p for p in model.parameters() if id(p) not in head_ids]
         return _Both(OverlappedGradAllReduce(head.hip_plan(), device, group=group), GradAllReduce(rest, group=group))
+    if on_gpu and hasattr(model, "hip_plans"):
+        plans = list(reversed(model.hip_plans()))
+        covered = {id(p) for plan in plans for p in plan.params}
+        rest = [p for p in model.parameters() if id(p) not in covered]
+        reducers = [OverlappedGradAllReduce(plan, device, group=group) for plan in plans]
+        return _Both(*reducers, *([GradAllReduce(rest, group=group)] if rest else []))
     return GradAllReduce(model.parameters(), group=group)
