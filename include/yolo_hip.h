@@ -288,6 +288,8 @@ int yolo_maxpool3s2_fwd(const yolo_pool_desc *d, const void *x_bf16, void *y_bf1
  * (first maximum in row-major order, recomputed from x) is (h, w).  d->out_halo = halo of dy, dx_halo = halo of dx. */
 int yolo_maxpool3s2_bwd(const yolo_pool_desc *d, const void *x_bf16, const void *dy_bf16, void *dx_bf16, int dx_halo,
                         yolo_stream_t stream);
+/* yolo_maxpool2_fwd and yolo_maxpool2_bwd_lrelu take an odd H or W with MaxPool2d's floor rule: the pooled map is [H/2][W/2], the last
+ * row / column belongs to no window, and the backward does not write it (dz must hold zeros there: a fresh workspace buffer does). */
 int yolo_maxpool2_fwd(const yolo_pool_desc *d, const void *x_bf16, void *y_bf16, yolo_stream_t stream);
 int yolo_maxpool2_bwd_lrelu(const yolo_pool_desc *d, const void *yfull_bf16, const void *dpool_bf16,
                             float slope, void *dz_bf16, yolo_stream_t stream);
@@ -635,6 +637,30 @@ int yolo_batchnorm_bwd(void *dy_bf16, int dy_halo, const void *y_bf16, int y_hal
                        int N, int H, int W, int C, const float *gamma, const float *mean_invstd, void *dz_bf16,
                        long dz_img_stride, long dz_row_stride, long dz_px_stride, long dz_off, int store_masked_dy,
                        int relu_from_z, float *dgamma, float *dbeta, double *acc2c, float *coef3c, yolo_stream_t stream);
+
+/* conv -> BatchNorm2d -> LeakyReLU(slope) [-> MaxPool2d(2,2)] units of the BatchNorm variant of the YOLOv1 network (Darknet's
+ * yolov1.cfg: batch_normalize=1 on every convolution).  Replaces aten batch_norm(training=True / False) + leaky_relu
+ * [+ max_pool2d(2, 2)] and, backward, max_pool2d_with_indices_backward + leaky_relu_backward + native_batch_norm_backward.
+ * Statistics, finalisation, running statistics, stats_ready 0 / 1 / 2 and save_mean_invstd exactly as yolo_batchnorm_train_fwd.
+ *   y = t > 0 ? t : slope * t,  t = fma(z, scale, shift),  one bf16 rounding.
+ * z is never written (always kept), `out` is required.  pool2 = 1: `out` is the pooled map [N][H/2 + 2*out_halo][W/2 + 2*out_halo][C],
+ * the maximum over the bf16-ROUNDED y of each 2x2 window (what yolo_maxpool2_fwd over a stored y gives, bit for bit); the un-pooled y
+ * is never written.  H and W must be even then (YOLO_E_UNSUPPORTED otherwise: run pool2 = 0 and yolo_maxpool2_fwd). */
+int yolo_batchnorm_train_fwd_lrelu(const void *z_bf16, int N, int H, int W, int C, int halo, const float *gamma,
+                                   const float *beta, double eps, double momentum, float *running_mean,
+                                   float *running_var, float slope, int pool2, double *acc2c, float *scale_shift,
+                                   void *out_bf16, int out_halo, float *save_mean_invstd, int stats_ready,
+                                   yolo_stream_t stream);
+/* Its backward.  The activation mask is recomputed from z with the forward's own fma(z, scale, shift) > 0 (mean_invstd = the 4*C floats the
+ * forward saved); no y is read.  dy' = dy * (t > 0 ? 1 : slope).  pool2 = 1: dy is the gradient of the POOLED map, in pooled geometry
+ * [N][H/2 + 2*dy_halo][W/2 + 2*dy_halo][C]; the four bf16-rounded y of a window are rebuilt from z, the gradient goes to the first
+ * maximum in scan order (the rule of yolo_maxpool2_bwd_lrelu and of aten), the other three elements have dy' = 0.  dbeta, dgamma, dz,
+ * the dz strides (zero-stuffed for a stride-2 conv), acc2c and coef3c as yolo_batchnorm_bwd; frozen = 1: the forward ran with
+ * stats_ready = 2 and the two batch terms drop out.  H, W = un-pooled size of z. */
+int yolo_batchnorm_bwd_lrelu(const void *dy_bf16, int dy_halo, const void *z_bf16, int z_halo, int N, int H, int W, int C,
+                             const float *gamma, const float *mean_invstd, float slope, int pool2, void *dz_bf16,
+                             long dz_img_stride, long dz_row_stride, long dz_px_stride, long dz_off, int frozen,
+                             float *dgamma, float *dbeta, double *acc2c, float *coef3c, yolo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * TP / FP matching of mAPMetric on the device.  Replaces the per-class greedy matching loops of

@@ -303,6 +303,199 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(bf16_t *__restrict__ 
     if (store_masked) *reinterpret_cast<uint4 *>(gq) = uint4{m[0], m[1], m[2], m[3]};
 }
 
+// ---- conv -> BatchNorm -> LeakyReLU(slope) [-> MaxPool2d(2,2)] units of the BatchNorm variant of the YOLOv1 network (Darknet's yolov1.cfg has
+// batch_normalize=1 on every convolution).  Statistics and finalisation are the kernels above; the apply passes below take the activation slope,
+// recompute the activation from z with the forward's own fma (no y is read in the backward), and, with POOL, work on 2x2 windows: the forward writes
+// only the pooled map (the maximum of the four bf16-ROUNDED activations, what a separate pool over the stored y would give), the backward rebuilds the
+// four rounded activations of a window from z and sends the pooled gradient to the first maximum in scan order (yolo_maxpool2_bwd_lrelu's and aten's rule).
+__device__ __forceinline__ float bn_lrelu_y(float z, float sc, float sh, float slope, float &dmul)
+{
+    const float t = fmaf(z, sc, sh);
+    dmul = t > 0.0f ? 1.0f : slope;
+    return bf16_to_f32(f32_to_bf16(t > 0.0f ? t : slope * t));
+}
+
+// window position (0..3 = 2*dy + dx) of the first maximum of y[0..3]
+__device__ __forceinline__ int bn_first_max4(const float y[4])
+{
+    int b = 0;
+    float m = y[0];
+#pragma unroll
+    for (int j = 1; j < 4; ++j)
+        if (y[j] > m) { m = y[j]; b = j; }
+    return b;
+}
+
+template <int POOL>
+__global__ void __launch_bounds__(256) bn_lrelu_apply_kernel(const bf16_t *__restrict__ z, int N, int H, int W, int C, int halo, const float *__restrict__ scale,
+                                                             const float *__restrict__ shift, float slope, bf16_t *__restrict__ out, int out_halo)
+{
+    const int C8 = C >> 3;
+    const int Ho = POOL ? H >> 1 : H, Wo = POOL ? W >> 1 : W;
+    const long total = (long)N * Ho * Wo * C8;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int cg = (int)(idx % C8);
+    const long p = idx / C8;
+    const int x = (int)(p % Wo), y = (int)((p / Wo) % Ho), n = (int)(p / ((long)Wo * Ho));
+    const int Hp = H + 2 * halo, Wp = W + 2 * halo;
+    const int step = POOL ? 2 : 1;
+    const bf16_t *q = z + (((long)n * Hp + step * y + halo) * Wp + step * x + halo) * C + cg * 8;
+    float sc[8], sh[8], r[8], dm;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { sc[k] = scale[cg * 8 + k]; sh[k] = shift[cg * 8 + k]; }
+    if (POOL) {
+        float f[4][8];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bn_unpack8(*reinterpret_cast<const uint4 *>(q + ((long)(j >> 1) * Wp + (j & 1)) * C), f[j]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            float m = bn_lrelu_y(f[0][k], sc[k], sh[k], slope, dm);
+#pragma unroll
+            for (int j = 1; j < 4; ++j) {
+                const float v = bn_lrelu_y(f[j][k], sc[k], sh[k], slope, dm);
+                m = v > m ? v : m;
+            }
+            r[k] = m;
+        }
+    } else {
+        float f[8];
+        bn_unpack8(*reinterpret_cast<const uint4 *>(q), f);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) r[k] = bn_lrelu_y(f[k], sc[k], sh[k], slope, dm);
+    }
+    unsigned o[4];
+#pragma unroll
+    for (int k = 0; k < 8; k += 2) o[k >> 1] = (unsigned)f32_to_bf16(r[k]) | ((unsigned)f32_to_bf16(r[k + 1]) << 16);      // r is a bf16 value: exact
+    const int Hq = Ho + 2 * out_halo, Wq = Wo + 2 * out_halo;
+    *reinterpret_cast<uint4 *>(out + (((long)n * Hq + y + out_halo) * Wq + x + out_halo) * C + cg * 8) = uint4{o[0], o[1], o[2], o[3]};
+}
+
+// dy' of the four elements of one window (POOL) or of one element: g[j][k], from the z vectors vz[j] and the gradient vector vg
+template <int POOL>
+__device__ __forceinline__ void bn_lrelu_grad(const uint4 &vg, const uint4 *vz, const float sc[8], const float sh[8], float slope, float zz[POOL ? 4 : 1][8],
+                                              float g[POOL ? 4 : 1][8])
+{
+    float d[8], dm;
+    bn_unpack8(vg, d);
+    if (POOL) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bn_unpack8(vz[j], zz[j]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            float y[4], mul[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) y[j] = bn_lrelu_y(zz[j][k], sc[k], sh[k], slope, mul[j]);
+            const int b = bn_first_max4(y);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) g[j][k] = j == b ? d[k] * mul[j] : 0.0f;
+        }
+    } else {
+        bn_unpack8(vz[0], zz[0]);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            bn_lrelu_y(zz[0][k], sc[k], sh[k], slope, dm);
+            g[0][k] = d[k] * dm;
+        }
+    }
+}
+
+// POOL: a lane walks POOLED pixels (dy's geometry) and loads the four z vectors of the window
+template <int POOL>
+__global__ void __launch_bounds__(256) bn_lrelu_bwd_reduce_kernel(const bf16_t *__restrict__ dy, int dy_halo, const bf16_t *__restrict__ z, int z_halo, int N, int H,
+                                                                  int W, int C, const float *__restrict__ mean_invstd, float slope, double *__restrict__ acc)
+{
+    constexpr int NW = POOL ? 4 : 1;
+    const int C8 = C >> 3;
+    const int gpb = C8 < 256 ? C8 : 256;
+    const int ppb = 256 / gpb;
+    const int cg = blockIdx.x * gpb + threadIdx.x % gpb, pl = threadIdx.x / gpb;
+    const int Hd = POOL ? H >> 1 : H, Wd = POOL ? W >> 1 : W, step = POOL ? 2 : 1;
+    const long P = (long)N * Hd * Wd;
+    const long zrow = (long)(W + 2 * z_halo) * C;
+    float s[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ss[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    if (cg < C8 && pl < ppb) {
+        float mu[8], is[8], sc[8], sh[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            mu[k] = mean_invstd[cg * 8 + k]; is[k] = mean_invstd[C + cg * 8 + k];
+            sc[k] = mean_invstd[2 * C + cg * 8 + k]; sh[k] = mean_invstd[3 * C + cg * 8 + k];
+        }
+        const long stride = (long)gridDim.y * ppb;
+        long p = (long)blockIdx.y * ppb + pl;
+        PixIter it(p < P ? p : 0, stride, Hd, Wd);
+        for (; p < P; p += stride) {
+            const uint4 vg = *reinterpret_cast<const uint4 *>(dy + it.off(dy_halo, C) + cg * 8);
+            const bf16_t *zq = z + (((long)it.n * (H + 2 * z_halo) + step * it.y + z_halo) * (W + 2 * z_halo) + step * it.x + z_halo) * C + cg * 8;
+            uint4 vz[NW];
+#pragma unroll
+            for (int j = 0; j < NW; ++j) vz[j] = *reinterpret_cast<const uint4 *>(zq + (j >> 1) * zrow + (j & 1) * C);
+            it.next();
+            float zz[NW][8], g[NW][8];
+            bn_lrelu_grad<POOL>(vg, vz, sc, sh, slope, zz, g);
+#pragma unroll
+            for (int j = 0; j < NW; ++j)
+#pragma unroll
+                for (int k = 0; k < 8; ++k) { s[k] += g[j][k]; ss[k] += g[j][k] * ((zz[j][k] - mu[k]) * is[k]); }
+        }
+    }
+    __shared__ float red[2][256][9];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { red[0][threadIdx.x][k] = s[k]; red[1][threadIdx.x][k] = ss[k]; }
+    __syncthreads();
+    if (pl == 0 && cg < C8) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            double a = 0.0, b = 0.0;
+            for (int r = 0; r < ppb; ++r) { a += red[0][r * gpb + threadIdx.x][k]; b += red[1][r * gpb + threadIdx.x][k]; }
+            double *rep = acc + (size_t)(blockIdx.y % YOLO_BN_ACC_REPLICAS) * 2 * C;
+            atomicAdd(rep + cg * 8 + k, a);
+            atomicAdd(rep + C + cg * 8 + k, b);
+        }
+    }
+}
+
+template <int POOL>
+__global__ void __launch_bounds__(256) bn_lrelu_bwd_apply_kernel(const bf16_t *__restrict__ dy, int dy_halo, const bf16_t *__restrict__ z, int z_halo, int N, int H,
+                                                                 int W, int C, const float *__restrict__ mean_invstd, const float *__restrict__ coef, float slope,
+                                                                 bf16_t *__restrict__ dz, long dz_img, long dz_row, long dz_px, long dz_off)
+{
+    constexpr int NW = POOL ? 4 : 1;
+    const int C8 = C >> 3;
+    const int Hd = POOL ? H >> 1 : H, Wd = POOL ? W >> 1 : W, step = POOL ? 2 : 1;
+    const long total = (long)N * Hd * Wd * C8;
+    const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= total) return;
+    const int cg = (int)(idx % C8);
+    const long p = idx / C8;
+    const int x = (int)(p % Wd), y = (int)((p / Wd) % Hd), n = (int)(p / ((long)Wd * Hd));
+    const long zrow = (long)(W + 2 * z_halo) * C;
+    const uint4 vg = *reinterpret_cast<const uint4 *>(dy + (((long)n * (Hd + 2 * dy_halo) + y + dy_halo) * (Wd + 2 * dy_halo) + x + dy_halo) * C + cg * 8);
+    const bf16_t *zq = z + (((long)n * (H + 2 * z_halo) + step * y + z_halo) * (W + 2 * z_halo) + step * x + z_halo) * C + cg * 8;
+    uint4 vz[NW];
+#pragma unroll
+    for (int j = 0; j < NW; ++j) vz[j] = *reinterpret_cast<const uint4 *>(zq + (j >> 1) * zrow + (j & 1) * C);
+    float sc[8], sh[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) { sc[k] = mean_invstd[2 * C + cg * 8 + k]; sh[k] = mean_invstd[3 * C + cg * 8 + k]; }
+    float zz[NW][8], g[NW][8];
+    bn_lrelu_grad<POOL>(vg, vz, sc, sh, slope, zz, g);
+#pragma unroll
+    for (int j = 0; j < NW; ++j) {
+        unsigned o[4];
+#pragma unroll
+        for (int k = 0; k < 8; k += 2) {
+            const int c = cg * 8 + k;
+            const float x0 = (zz[j][k] - mean_invstd[c]) * mean_invstd[C + c], x1 = (zz[j][k + 1] - mean_invstd[c + 1]) * mean_invstd[C + c + 1];
+            const float d0 = coef[c] * (g[j][k] - coef[C + c] - x0 * coef[2 * C + c]);
+            const float d1 = coef[c + 1] * (g[j][k + 1] - coef[C + c + 1] - x1 * coef[2 * C + c + 1]);
+            o[k >> 1] = (unsigned)f32_to_bf16(d0) | ((unsigned)f32_to_bf16(d1) << 16);
+        }
+        *reinterpret_cast<uint4 *>(dz + (long)n * dz_img + (long)(step * y + (j >> 1)) * dz_row + (long)(step * x + (j & 1)) * dz_px + dz_off + cg * 8) =
+            uint4{o[0], o[1], o[2], o[3]};
+    }
+}
+
 }  // namespace yolo
 
 using namespace yolo;
@@ -362,4 +555,70 @@ YOLO_API int yolo_batchnorm_bwd(void *dy, int dy_halo, const void *y, int y_halo
     hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (bf16_t *)dy, dy_halo, (const bf16_t *)y, y_halo, (const bf16_t *)z,
                        z_halo, N, H, W, C, mean_invstd, coef3c, (bf16_t *)dz, dz_img_stride, dz_row_stride, dz_px_stride, dz_off, store_masked_dy, relu_from_z);
     return check_launch("yolo_batchnorm_bwd(apply)");
+}
+
+YOLO_API int yolo_batchnorm_train_fwd_lrelu(const void *z, int N, int H, int W, int C, int halo, const float *gamma, const float *beta, double eps, double momentum,
+                                            float *running_mean, float *running_var, float slope, int pool2, double *acc2c, float *scale_shift, void *out,
+                                            int out_halo, float *save_mean_invstd, int stats_ready, yolo_stream_t stream)
+{
+    if (!z || !gamma || !beta || !acc2c || !scale_shift || !out || N <= 0 || H <= 0 || W <= 0 || C <= 0 || halo < 0 || out_halo < 0 || (pool2 != 0 && pool2 != 1))
+        return fail(YOLO_E_ARG, "yolo_batchnorm_train_fwd_lrelu: bad argument (out is required: z is always kept; pool2 is 0 or 1)");
+    if (C & 7) return fail(YOLO_E_UNSUPPORTED, "yolo_batchnorm_train_fwd_lrelu: C = %d must be a multiple of 8", C);
+    if (pool2 && ((H | W) & 1)) return fail(YOLO_E_UNSUPPORTED, "yolo_batchnorm_train_fwd_lrelu: pool2 needs an even map, got %d x %d (pool2 = 0, then yolo_maxpool2_fwd)", H, W);
+    if ((running_mean == nullptr) != (running_var == nullptr)) return fail(YOLO_E_ARG, "yolo_batchnorm_train_fwd_lrelu: running_mean and running_var go together");
+    if (stats_ready < 0 || stats_ready > 2 || (stats_ready == 2 && !running_mean))
+        return fail(YOLO_E_ARG, "yolo_batchnorm_train_fwd_lrelu: stats_ready is 0, 1 or 2 (2 = normalise with the running statistics, which must be given)");
+    hipStream_t s = STRM(stream);
+    const int C8 = C / 8, gpb = C8 < 256 ? C8 : 256, ppb = 256 / gpb;
+    const long P = (long)N * H * W;
+    long gy = (P + (long)ppb * 32 - 1) / ((long)ppb * 32);
+    if (gy > 2048) gy = 2048;
+    if (gy < 1) gy = 1;
+    if (!stats_ready) {
+        hipLaunchKernelGGL(bn_stats_kernel, dim3((C8 + gpb - 1) / gpb, (unsigned)gy), dim3(256), 0, s, (const bf16_t *)z, N, H, W, C, halo, acc2c);
+        if (int rc = check_launch("yolo_batchnorm_train_fwd_lrelu(stats)")) return rc;
+    }
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, acc2c, C, (double)P, gamma, beta, eps, momentum, running_mean, running_var, scale_shift,
+                       scale_shift + C, save_mean_invstd, stats_ready == 2 ? 1 : 0);
+    if (int rc = check_launch("yolo_batchnorm_train_fwd_lrelu(finalize)")) return rc;
+    const long total = (pool2 ? P / 4 : P) * C8;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (pool2)
+        hipLaunchKernelGGL(bn_lrelu_apply_kernel<1>, grid, dim3(256), 0, s, (const bf16_t *)z, N, H, W, C, halo, scale_shift, scale_shift + C, slope, (bf16_t *)out, out_halo);
+    else
+        hipLaunchKernelGGL(bn_lrelu_apply_kernel<0>, grid, dim3(256), 0, s, (const bf16_t *)z, N, H, W, C, halo, scale_shift, scale_shift + C, slope, (bf16_t *)out, out_halo);
+    return check_launch("yolo_batchnorm_train_fwd_lrelu(apply)");
+}
+
+YOLO_API int yolo_batchnorm_bwd_lrelu(const void *dy, int dy_halo, const void *z, int z_halo, int N, int H, int W, int C, const float *gamma, const float *mean_invstd,
+                                      float slope, int pool2, void *dz, long dz_img_stride, long dz_row_stride, long dz_px_stride, long dz_off, int frozen,
+                                      float *dgamma, float *dbeta, double *acc2c, float *coef3c, yolo_stream_t stream)
+{
+    if (!dy || !z || !gamma || !mean_invstd || !dz || !dgamma || !dbeta || !acc2c || !coef3c || N <= 0 || H <= 0 || W <= 0 || C <= 0 || dy_halo < 0 || z_halo < 0 ||
+        (pool2 != 0 && pool2 != 1) || (frozen != 0 && frozen != 1))
+        return fail(YOLO_E_ARG, "yolo_batchnorm_bwd_lrelu: bad argument (pool2 and frozen are 0 or 1)");
+    if ((C & 7) || (dz_img_stride & 7) || (dz_row_stride & 7) || (dz_px_stride & 7) || (dz_off & 7))
+        return fail(YOLO_E_UNSUPPORTED, "yolo_batchnorm_bwd_lrelu: C = %d and the dz strides must be multiples of 8", C);
+    if (pool2 && ((H | W) & 1)) return fail(YOLO_E_UNSUPPORTED, "yolo_batchnorm_bwd_lrelu: pool2 needs an even map, got %d x %d", H, W);
+    hipStream_t s = STRM(stream);
+    const int C8 = C / 8, gpb = C8 < 256 ? C8 : 256, ppb = 256 / gpb;
+    const long P = (long)N * H * W, Pd = pool2 ? P / 4 : P;          // Pd: pixels of dy, which the reduction's lanes walk
+    long gy = (Pd + (long)ppb * 32 - 1) / ((long)ppb * 32);
+    if (gy > 2048) gy = 2048;
+    if (gy < 1) gy = 1;
+    const dim3 rgrid((C8 + gpb - 1) / gpb, (unsigned)gy), agrid((unsigned)((Pd * C8 + 255) / 256));
+    if (pool2)
+        hipLaunchKernelGGL(bn_lrelu_bwd_reduce_kernel<1>, rgrid, dim3(256), 0, s, (const bf16_t *)dy, dy_halo, (const bf16_t *)z, z_halo, N, H, W, C, mean_invstd, slope, acc2c);
+    else
+        hipLaunchKernelGGL(bn_lrelu_bwd_reduce_kernel<0>, rgrid, dim3(256), 0, s, (const bf16_t *)dy, dy_halo, (const bf16_t *)z, z_halo, N, H, W, C, mean_invstd, slope, acc2c);
+    if (int rc = check_launch("yolo_batchnorm_bwd_lrelu(reduce)")) return rc;
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3((C + 255) / 256), dim3(256), 0, s, acc2c, C, (double)P, gamma, mean_invstd, dgamma, dbeta, coef3c, frozen);
+    if (int rc = check_launch("yolo_batchnorm_bwd_lrelu(finalize)")) return rc;
+    if (pool2)
+        hipLaunchKernelGGL(bn_lrelu_bwd_apply_kernel<1>, agrid, dim3(256), 0, s, (const bf16_t *)dy, dy_halo, (const bf16_t *)z, z_halo, N, H, W, C, mean_invstd, coef3c, slope,
+                           (bf16_t *)dz, dz_img_stride, dz_row_stride, dz_px_stride, dz_off);
+    else
+        hipLaunchKernelGGL(bn_lrelu_bwd_apply_kernel<0>, agrid, dim3(256), 0, s, (const bf16_t *)dy, dy_halo, (const bf16_t *)z, z_halo, N, H, W, C, mean_invstd, coef3c, slope,
+                           (bf16_t *)dz, dz_img_stride, dz_row_stride, dz_px_stride, dz_off);
+    return check_launch("yolo_batchnorm_bwd_lrelu(apply)");
 }

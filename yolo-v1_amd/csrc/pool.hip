@@ -163,16 +163,20 @@ __global__ void __launch_bounds__(256) maxpool2_bwd_codes_kernel(const bf16_t *_
 
 using namespace yolo;
 
-static int pool_args(const yolo_pool_desc *d, const char *who)
+// odd_ok: the 2x2 kernels that address the un-pooled map themselves take an odd H or W with MaxPool2d's floor rule: the pooled map is
+// [H/2][W/2], the last row / column belongs to no window (the backward leaves it as it finds it: zero in a workspace buffer)
+static int pool_args(const yolo_pool_desc *d, const char *who, bool odd_ok = false)
 {
     if (!d || d->N <= 0 || d->H <= 0 || d->W <= 0 || d->C <= 0 || d->in_halo < 0 || d->out_halo < 0) return fail(YOLO_E_ARG, "%s: bad descriptor", who);
-    if ((d->C & 7) || (d->H & 1) || (d->W & 1)) return fail(YOLO_E_UNSUPPORTED, "%s: C=%d must be a multiple of 8 and H,W=%d,%d even", who, d->C, d->H, d->W);
+    if ((d->C & 7) || (!odd_ok && ((d->H & 1) || (d->W & 1))))
+        return fail(YOLO_E_UNSUPPORTED, "%s: C=%d must be a multiple of 8 and H,W=%d,%d even", who, d->C, d->H, d->W);
+    if (odd_ok && (d->H < 2 || d->W < 2)) return fail(YOLO_E_UNSUPPORTED, "%s: H,W=%d,%d hold no 2x2 window", who, d->H, d->W);
     return 0;
 }
 
 YOLO_API int yolo_maxpool2_fwd(const yolo_pool_desc *d, const void *x, void *y, yolo_stream_t stream)
 {
-    if (int rc = pool_args(d, "yolo_maxpool2_fwd")) return rc;
+    if (int rc = pool_args(d, "yolo_maxpool2_fwd", true)) return rc;
     if (!x || !y) return fail(YOLO_E_ARG, "yolo_maxpool2_fwd: null pointer");
     const long total = (long)d->N * (d->H / 2) * (d->W / 2) * (d->C / 8);
     hipLaunchKernelGGL(maxpool2_fwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, STRM(stream), (const bf16_t *)x, d->N, d->H, d->W, d->C,
@@ -182,7 +186,7 @@ YOLO_API int yolo_maxpool2_fwd(const yolo_pool_desc *d, const void *x, void *y, 
 
 YOLO_API int yolo_maxpool2_bwd_lrelu(const yolo_pool_desc *d, const void *yfull, const void *dpool, float slope, void *dz, yolo_stream_t stream)
 {
-    if (int rc = pool_args(d, "yolo_maxpool2_bwd_lrelu")) return rc;
+    if (int rc = pool_args(d, "yolo_maxpool2_bwd_lrelu", true)) return rc;
     if (!yfull || !dpool || !dz) return fail(YOLO_E_ARG, "yolo_maxpool2_bwd_lrelu: null pointer");
     const long total = (long)d->N * (d->H / 2) * (d->W / 2) * (d->C / 8);
     hipLaunchKernelGGL(maxpool2_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, STRM(stream), (const bf16_t *)yfull, (const bf16_t *)dpool,

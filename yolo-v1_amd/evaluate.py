@@ -28,14 +28,20 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--output", default="evaluation_results.txt")
     ap.add_argument("--use-ema", action="store_true", help="evaluate the averaged weights of a train.py --ema-decay checkpoint (ema_state_dict)")
+    ap.add_argument("--batch-norm", action="store_true",
+                    help="--backbone yolov1 without a checkpoint: the BatchNorm variant (a checkpoint's own batch_norm record decides otherwise)")
     a = ap.parse_args()
+    ck = torch.load(a.checkpoint, map_location=a.device, weights_only=True) if a.checkpoint else None
+    bn = bool(ck.get("batch_norm", False)) if ck is not None else a.batch_norm
+    if bn and a.backbone != "yolov1":
+        ap.error("batch_norm (the checkpoint's record, or --batch-norm) needs --backbone yolov1")
     ds = SyntheticYOLODataset(a.synthetic, seed=2) if a.synthetic else create_voc_datasets([("2007", "test")], augment=False)
     loader = DataLoader(ds, batch_size=a.batch_size, shuffle=False, num_workers=4)
-    bb = YOLOv1Backbone() if a.backbone == "yolov1" else ResNetBackbone(pretrained=False)
+    bb = (YOLOv1Backbone(batch_norm=True) if bn else YOLOv1Backbone()) if a.backbone == "yolov1" else ResNetBackbone(pretrained=False)
     model = YOLOv1(backbone=bb, num_classes=20)
     if a.checkpoint:
         from yolo.training.checkpoints import weights_of
-        model.load_state_dict(weights_of(torch.load(a.checkpoint, map_location=a.device, weights_only=True), a.use_ema, a.checkpoint))
+        model.load_state_dict(weights_of(ck, a.use_ema, a.checkpoint))
     elif a.use_ema:
         ap.error("--use-ema needs --checkpoint")
     model = model.to(a.device)

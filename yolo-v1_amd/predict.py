@@ -19,11 +19,17 @@ from yolo.inference import YOLOInference  # noqa: E402
 from yolo.utils import VOC_CLASSES, draw_detections  # noqa: E402
 
 
-def load_model(checkpoint_path: str | None, device: str, num_classes: int = 20, backbone: str = "resnet50", use_ema: bool = False) -> YOLOv1:
-    bb = YOLOv1Backbone() if backbone == "yolov1" else ResNetBackbone(pretrained=False)
+def load_model(checkpoint_path: str | None, device: str, num_classes: int = 20, backbone: str = "resnet50", use_ema: bool = False,
+               batch_norm: bool = False) -> YOLOv1:
+    """batch_norm: the BatchNorm variant of --backbone yolov1 when there is no checkpoint; a checkpoint's own ``batch_norm`` record decides otherwise"""
+    ck = torch.load(checkpoint_path, map_location=device, weights_only=True) if checkpoint_path else None
+    if ck is not None:
+        batch_norm = bool(ck.get("batch_norm", False))
+    if batch_norm and backbone != "yolov1":
+        raise SystemExit("batch_norm (the checkpoint's record, or --batch-norm) needs --backbone yolov1")
+    bb = (YOLOv1Backbone(batch_norm=True) if batch_norm else YOLOv1Backbone()) if backbone == "yolov1" else ResNetBackbone(pretrained=False)
     model = YOLOv1(backbone=bb, num_classes=num_classes)
     if checkpoint_path:
-        ck = torch.load(checkpoint_path, map_location=device, weights_only=True)
         from yolo.training.checkpoints import weights_of
         model.load_state_dict(weights_of(ck, use_ema, checkpoint_path))
     elif use_ema:
@@ -41,8 +47,10 @@ def main():
     ap.add_argument("--nms-threshold", type=float, default=0.4)
     ap.add_argument("--output-dir", default=None)
     ap.add_argument("--use-ema", action="store_true", help="load the averaged weights of a train.py --ema-decay checkpoint (ema_state_dict)")
+    ap.add_argument("--batch-norm", action="store_true",
+                    help="--backbone yolov1 without a checkpoint: the BatchNorm variant (a checkpoint's own batch_norm record decides otherwise)")
     a = ap.parse_args()
-    engine = YOLOInference(load_model(a.checkpoint, a.device, backbone=a.backbone, use_ema=a.use_ema), device=a.device)
+    engine = YOLOInference(load_model(a.checkpoint, a.device, backbone=a.backbone, use_ema=a.use_ema, batch_norm=a.batch_norm), device=a.device)
     for path in a.images:
         dets = engine.predict(path, conf_threshold=a.conf_threshold, nms_threshold=a.nms_threshold, class_names=VOC_CLASSES)
         print(f"{path}: {len(dets)} detections")

@@ -86,6 +86,9 @@ def main():
     ap.add_argument("--checkpoint-dir", default="checkpoints_pretrain")
     ap.add_argument("--save-frequency", type=int, default=10)
     ap.add_argument("--resume", default=None)
+    ap.add_argument("--batch-norm", action="store_true",
+                    help="Conv2d(bias=False) + BatchNorm2d + LeakyReLU(0.1) in place of Conv2d + LeakyReLU(0.1) on every convolution of the YOLOv1 network (Darknet's "
+                         "batch_normalize=1): trains from the default initialisation.  Recorded in the checkpoint; --resume and --backbone-weights check it")
     a = ap.parse_args()
     if bool(a.synthetic) == bool(a.data_root):
         ap.error("give exactly one of --data-root and --synthetic")
@@ -95,6 +98,9 @@ def main():
         ap.error("--accum-steps must be at least 1")
     if a.image_size < 32 or a.image_size % 32:
         ap.error("--image-size must be a multiple of 32 (the trunk halves the map five times)")
+    if a.deterministic and a.batch_norm:
+        from yolo.bn_executor import BN_LRELU_NOT_DETERMINISTIC
+        ap.error("--deterministic --batch-norm: " + BN_LRELU_NOT_DETERMINISTIC)
     if a.deterministic:
         from yolo.config import CONFIG
         CONFIG.DETERMINISTIC = True
@@ -142,7 +148,7 @@ def main():
     val_loader = DataLoader(val_ds, batch_size=a.batch_size, shuffle=False, num_workers=a.num_workers, pin_memory=pin, collate_fn=collate,
                             worker_init_fn=worker_init)
 
-    model = YOLOv1Classifier(num_classes=classes)
+    model = YOLOv1Classifier(num_classes=classes, batch_norm=True) if a.batch_norm else YOLOv1Classifier(num_classes=classes)
     if a.init == "kaiming" and not a.resume:
         init_kaiming_(model)
     model = model.to(device)
@@ -171,6 +177,9 @@ def main():
         ck = torch.load(a.resume, map_location=device, weights_only=True)
         if ck.get("num_classes", classes) != classes:
             ap.error(f"--resume {a.resume} was trained with {ck['num_classes']} classes, this run has {classes}")
+        if bool(ck.get("batch_norm", False)) != a.batch_norm:
+            ap.error(f"--resume {a.resume} records batch_norm={bool(ck.get('batch_norm', False))}, this run has batch_norm={a.batch_norm} "
+                     "(--batch-norm): the two must agree")
         model.load_state_dict(ck["model_state_dict"])
         optimizer.load_state_dict(ck["optimizer_state_dict"])
         if "scheduler_state_dict" in ck:
@@ -197,6 +206,8 @@ def main():
         extra["accum_steps"] = a.accum_steps
     if a.init != "default":        # (the default: the checkpoint's keys are those of a run without the option)
         record["init"] = a.init
+    if a.batch_norm:               # (likewise)
+        record["batch_norm"] = True
     res = loop.train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, a.epochs, ckdir, save_frequency=a.save_frequency,
                      start_epoch=start_epoch, best_top1_init=best_top1, seed=a.seed, record=record, ema=ema, **extra)
     if rank == 0:

@@ -92,7 +92,15 @@ def main():
                          "layer as it is (yolo.models.init_kaiming_); applied before --backbone-weights, which then overwrites the 40 trunk tensors "
                          "(the four detection convolutions and FC1 keep it); --backbone resnet50: the head only.  --resume wins over it")
     ap.add_argument("--seed", type=int, default=None, help="seed of torch, numpy, random and the loaders (every epoch starts from (seed, epoch))")
+    ap.add_argument("--batch-norm", action="store_true",
+                    help="--backbone yolov1 only: " "Conv2d(bias=False) + BatchNorm2d + LeakyReLU(0.1) in place of Conv2d + LeakyReLU(0.1) on every convolution of the YOLOv1 network (Darknet's "
+                         "batch_normalize=1): trains from the default initialisation.  Recorded in the checkpoint; --resume and --backbone-weights check it")
     a = ap.parse_args()
+    if a.batch_norm and a.backbone != "yolov1":
+        ap.error("--batch-norm needs --backbone yolov1 (the ResNet-50 trunk has its BatchNorm layers already)")
+    if a.batch_norm and a.deterministic:
+        from yolo.bn_executor import BN_LRELU_NOT_DETERMINISTIC
+        ap.error("--deterministic --batch-norm: " + BN_LRELU_NOT_DETERMINISTIC)
     if a.accum_steps < 1:
         ap.error("--accum-steps must be at least 1")
     if a.augment != "reference" and a.synthetic:
@@ -143,13 +151,16 @@ def main():
     val_loader = DataLoader(val_ds, batch_size=a.batch_size, shuffle=False, num_workers=a.num_workers, pin_memory=device == "cuda", collate_fn=collate,
                             worker_init_fn=worker_init)
 
-    backbone = YOLOv1Backbone() if a.backbone == "yolov1" else ResNetBackbone(pretrained=not a.no_pretrained, freeze=a.freeze_backbone)
+    backbone = (YOLOv1Backbone(batch_norm=True) if a.batch_norm else YOLOv1Backbone()) if a.backbone == "yolov1" else ResNetBackbone(pretrained=not a.no_pretrained, freeze=a.freeze_backbone)
     model = YOLOv1(backbone=backbone, num_classes=20, S=7, B=2)
     if a.init == "kaiming" and not a.resume:
         from yolo.models import init_kaiming_
         init_kaiming_(model if a.backbone == "yolov1" else model.head)
     if a.backbone_weights and not a.resume:          # behind --init: the checkpoint's 40 trunk tensors replace whatever the trunk was given
         ck0 = torch.load(a.backbone_weights, map_location="cpu", weights_only=True)
+        if bool(ck0.get("batch_norm", False)) != a.batch_norm:
+            ap.error(f"--backbone-weights {a.backbone_weights} records batch_norm={bool(ck0.get('batch_norm', False))}, this run has "
+                     f"batch_norm={a.batch_norm} (--batch-norm): the two must agree")
         sd = ck0["ema_state_dict"] if (a.use_ema and "ema_state_dict" in ck0) else ck0["model_state_dict"]
         loaded = backbone.load_pretrained(sd)
         if rank == 0:
@@ -174,6 +185,8 @@ def main():
             optimizer.attach_plan(model.hip_plan(), overlap=a.accum_steps == 1)
         elif hasattr(model.head, "hip_plan"):          # DetectionHead on a ResNet trunk: its Linear layers' bf16 operands
             optimizer.attach_plan(model.head.hip_plan())
+        elif a.batch_norm:                             # the default head behind the BatchNorm chain: a plan of its own
+            optimizer.attach_plan(model.head_plan())
     elif a.optimizer == "sgd":
         optimizer = torch.optim.SGD(params, lr=a.lr, momentum=a.momentum, weight_decay=a.weight_decay, nesterov=a.nesterov)
     else:
@@ -183,6 +196,9 @@ def main():
     start_epoch, best_val, best_map = 1, None, None
     if a.resume:
         ck = torch.load(a.resume, map_location=device, weights_only=True)
+        if bool(ck.get("batch_norm", False)) != a.batch_norm:
+            ap.error(f"--resume {a.resume} records batch_norm={bool(ck.get('batch_norm', False))}, this run has batch_norm={a.batch_norm} "
+                     "(--batch-norm): the two must agree")
         model.load_state_dict(ck["model_state_dict"])
         optimizer.load_state_dict(ck["optimizer_state_dict"])
         if "scheduler_state_dict" in ck:
@@ -209,6 +225,8 @@ def main():
         record = {**(record or {}), "augment": a.augment}
     if a.init != "default":               # (likewise)
         record = {**(record or {}), "init": a.init}
+    if a.batch_norm:                      # (likewise)
+        record = {**(record or {}), "batch_norm": True}
     res = training.train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, a.epochs, ckdir,
                          save_frequency=a.save_frequency, compute_map=a.compute_map, start_epoch=start_epoch,
                          best_val_loss_init=best_val, best_map_init=best_map, seed=a.seed, record=record, ema=ema, **extra)

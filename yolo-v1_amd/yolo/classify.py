@@ -18,7 +18,7 @@ import torch.nn.functional as F
 from . import _hip, engine
 from ._hip import check, lib, ptr, stream
 from .loss import _COPY_STREAMS, LossParts
-from .models import YOLOv1Backbone, _PlanOwner
+from .models import YOLOv1Backbone, _BNFeatures, _load_features, _PlanOwner
 
 TRUNK_CONVS = 20             # convolutions of YOLOv1Backbone that the classifier shares with the detector (the paper's count)
 _KEYS = ("total", "top1", "top5")
@@ -211,13 +211,16 @@ class SoftmaxCrossEntropy(nn.Module):
 
 # ------------------------------------------------------------------------------------------------ the classifier
 def trunk_cut(features, convs: int = TRUNK_CONVS) -> int:
-    """number of leading modules of ``features`` up to and including the LeakyReLU behind its ``convs``-th Conv2d"""
+    """number of leading modules of ``features`` up to and including the [BatchNorm2d and] LeakyReLU behind its ``convs``-th Conv2d"""
     seen = 0
     for i, m in enumerate(features):
         if isinstance(m, nn.Conv2d):
             seen += 1
             if seen == convs:
-                return i + 2 if (i + 1 < len(features) and isinstance(features[i + 1], nn.LeakyReLU)) else i + 1
+                j = i + 1
+                if j < len(features) and isinstance(features[j], nn.BatchNorm2d):
+                    j += 1
+                return j + 1 if (j < len(features) and isinstance(features[j], nn.LeakyReLU)) else j
     raise ValueError(f"features hold {seen} convolutions, fewer than {convs}")
 
 
@@ -229,11 +232,13 @@ class YOLOv1Classifier(_PlanOwner, nn.Module):
     Device tensors: two engine plans -- the conv / pool trunk and [Flatten, Linear] -- with the ``GlobalAvgPool`` node between them;
     ``hip_plans()`` lists them in forward order, which is how ``parallel.make_grad_reducer`` and ``yolo.optim.GradAccumulator`` find them."""
 
-    def __init__(self, num_classes: int = 1000):
+    def __init__(self, num_classes: int = 1000, batch_norm: bool = False):
         super().__init__()
         self.num_classes = num_classes
-        full = YOLOv1Backbone().features
+        self.batch_norm = bool(batch_norm)
+        full = (YOLOv1Backbone(batch_norm=True) if self.batch_norm else YOLOv1Backbone()).features
         self.features = nn.Sequential(*list(full)[:trunk_cut(full)])
+        self._bn = _BNFeatures(self.features) if self.batch_norm else None
         self.pool = GlobalAvgPool()
         self.fc = nn.Linear(1024, num_classes)
         self._flatten = nn.Flatten()
@@ -241,6 +246,12 @@ class YOLOv1Classifier(_PlanOwner, nn.Module):
         self._plan: engine.Plan | None = None        # the plan with the Linear layer: the one _PlanOwner.__deepcopy__ waits for
 
     def trunk_plan(self) -> engine.Plan:
+        """the plan of the plain trunk; with batch_norm=True, of the trunk with its BatchNorm layers folded in (inference)"""
+        if self.batch_norm:
+            mods, fresh = self._bn.folded()
+            if self._trunk_plan is None or fresh:
+                self._trunk_plan = engine.Plan.from_modules(mods, 3, True)
+            return self._own(self._trunk_plan)
         if self._trunk_plan is None:
             self._trunk_plan = engine.Plan.from_modules(self.features, 3, True)
         return self._own(self._trunk_plan)
@@ -251,13 +262,19 @@ class YOLOv1Classifier(_PlanOwner, nn.Module):
         return self._own(self._plan)
 
     def hip_plans(self) -> list:
+        """the plans a training step updates; a BatchNorm trunk is none of them: its parameters travel through autograd (engine.BNPlan)"""
+        if self.batch_norm:
+            return [self.head_plan()]
         return [self.trunk_plan(), self.head_plan()]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         """x: (N, 3, H, W) fp32 images, or a ``yolo.augment.U8Batch`` (decoded uint8 images + crop / colour / flip parameters): on the device
         it is augmented straight into the trunk plan's stem input buffer, as ``YOLOv1.forward`` does; on the CPU its fp32 tensor is taken"""
         if x.is_cuda:
-            f = engine.run_plan(self.trunk_plan(), x, self.training)
+            if self.batch_norm and self._bn.wants_train_path(self.training):
+                f = engine.run_bn_plan(self._bn.train_plan(), x, self.training)
+            else:
+                f = engine.run_plan(self.trunk_plan(), x, self.training and not self.batch_norm)
             return engine.run_plan(self.head_plan(), self.pool(f), self.training)
         if not isinstance(x, torch.Tensor):
             x = x.to_tensor()

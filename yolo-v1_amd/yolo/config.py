@@ -30,6 +30,8 @@ class EngineConfig:
     PERSIST: bool = True             # plans with the persistent kernels (tile_hint 20 / 21) run them (False: the pipelined kernels 15 / 16 -- A/B runs)
     # ---- what is fused
     BN_STATS_IN_CONV: bool = True    # ResNet trunk in batch-statistics mode: BatchNorm's sums come out of the conv's epilogue (yolo_igemm_desc.bn_stats)
+    BN_POOL_FUSED: bool = True       # BatchNorm variant of YOLOv1 in training: the MaxPool2d(2,2) behind four of its layers inside the BatchNorm + LeakyReLU passes
+                                     # (yolo_batchnorm_*_lrelu pool2 = 1; False: the un-pooled y is stored and pooled by yolo_maxpool2_* -- A/B runs and tests)
     STEM_KERNEL: bool = True         # 7x7/s2 stem through yolo_conv_stem7_fwd (False: the generic row-segment implicit GEMM; tests compare)
     STEM_POOL_BWD_FUSED: bool = True # backward of the pool + LeakyReLU behind the stem inside yolo_wgrad_stem7_pooled (False: separate pass)
     STRIDE2_CLASSES: bool = True     # data gradient of a stride-2 3x3 conv as four parity-class convs over the non-zero gradient slots

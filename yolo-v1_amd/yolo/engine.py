@@ -5,6 +5,7 @@
     plans.py            launch plans of yolo_igemm: shipped table, deterministic default, tuner, ``igemm_call``
     executor.py         Layer / Plan: the YOLOv1 conv / pool / FC executor (forward, backward on two streams)
     resnet_executor.py  ResNetPlan: ResNet-50 trunk (inference, frozen-training, trainable forward / backward)
+    bn_executor.py      BNPlan: conv -> BatchNorm -> LeakyReLU [-> pool] chains of the BatchNorm YOLOv1 variant (training forward / backward)
     autograd.py         PlanFunction, ResNetTrainFunction, run_plan
 
 This module re-exports their names, and reads / writes of a switch (``engine.FUSE_POOL = False``, ``engine.TIMERS = []``) or of a runtime hook
@@ -16,12 +17,14 @@ import sys
 import types
 
 from . import autograd as _autograd
+from . import bn_executor as _bn_executor
 from . import config as _config
 from . import executor as _executor
 from . import plans as _plans
 from . import resnet_executor as _resnet_executor
 from . import runtime as _runtime
 from .autograd import PlanFunction, ResNetTrainFunction, run_plan  # noqa: F401
+from .bn_executor import BNPlan, BNTrainFunction, run_bn_plan  # noqa: F401
 from .config import CONFIG, EngineConfig  # noqa: F401
 from .executor import Layer, Plan  # noqa: F401
 from .plans import (PLAN_FILE, _TILE, _TILE_COST, _TUNED, _default_plan, _key_str, _persist_ok, _pipe_ok, _pipe_pool_ok, _run_plan_igemm,  # noqa: F401

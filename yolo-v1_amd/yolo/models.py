@@ -82,8 +82,82 @@ class Backbone(nn.Module):
         raise NotImplementedError("Subclasses must implement forward method")
 
 
-def _conv_act(cin: int, cout: int, k: int, stride: int = 1, pad: int = 0) -> list[nn.Module]:
+def _conv_act(cin: int, cout: int, k: int, stride: int = 1, pad: int = 0, bn: bool = False) -> list[nn.Module]:
+    if bn:          # Darknet's batch_normalize=1: the conv has no bias, BatchNorm's shift takes its place
+        return [nn.Conv2d(cin, cout, kernel_size=k, stride=stride, padding=pad, bias=False), nn.BatchNorm2d(cout), nn.LeakyReLU(0.1)]
     return [nn.Conv2d(cin, cout, kernel_size=k, stride=stride, padding=pad), nn.LeakyReLU(0.1)]
+
+
+class _BNFeatures:
+    """How a ``features`` stack with BatchNorm layers runs on the device (``YOLOv1Backbone(batch_norm=True)``, ``YOLOv1Classifier(.., batch_norm=True)``):
+    with gradients, the training executor ``engine.BNPlan`` (batch statistics in train(), running statistics in eval()); without, the BatchNorm layers
+    folded into plain ``[Conv2d(bias), LeakyReLU, MaxPool2d]`` modules that the ordinary ``engine.Plan`` runs -- same shapes, same launch table as the
+    plain network.  The folded modules are shadows outside the module tree (no state-dict keys); they are refreshed when a parameter's or buffer's
+    ``_version`` changes, as ``ResNetPlan._pack_all`` does."""
+
+    def __init__(self, features: nn.Sequential):
+        self.features = features
+        self.bn_plan: "engine.BNPlan | None" = None
+        self._shadow: list | None = None         # the folded plain modules, in order
+        self._pairs: list = []                   # (conv, bn, shadow conv)
+        self._ver = None
+
+    def wants_train_path(self, training: bool) -> bool:
+        """train(): batch statistics, whether or not gradients are recorded; eval(): only a forward that records gradients needs the kept z"""
+        return training or (torch.is_grad_enabled() and any(p.requires_grad for p in self.features.parameters()))
+
+    def train_plan(self) -> "engine.BNPlan":
+        if self.bn_plan is None:
+            self.bn_plan = engine.BNPlan.from_modules(self.features)
+        return self.bn_plan
+
+    def folded(self) -> tuple[list, bool]:
+        """(the folded plain modules with the current parameters and running statistics, whether the module objects are new)"""
+        mods = list(self.features)
+        dev = mods[0].weight.device
+        fresh = self._shadow is None or self._pairs[0][2].weight.device != dev
+        if fresh:
+            self._shadow, self._pairs, self._ver = [], [], None
+            i = 0
+            while i < len(mods):
+                m = mods[i]
+                if isinstance(m, nn.Conv2d) and i + 1 < len(mods) and isinstance(mods[i + 1], nn.BatchNorm2d):
+                    sh = nn.Conv2d(m.in_channels, m.out_channels, m.kernel_size, m.stride, m.padding, bias=True, device="meta")
+                    sh = sh.to_empty(device=dev).requires_grad_(False)
+                    self._pairs.append((m, mods[i + 1], sh))
+                    self._shadow.append(sh)
+                    i += 2
+                else:
+                    self._shadow.append(m)
+                    i += 1
+        ver = tuple(int(t._version) for t in self.features.parameters()) + tuple(int(b._version) for b in self.features.buffers())
+        if ver != self._ver:
+            with torch.no_grad():
+                for conv, bn, sh in self._pairs:
+                    w, b = engine.ResNetPlan._fold(conv, bn)
+                    sh.weight.copy_(w)
+                    sh.bias.copy_(b)
+            self._ver = ver
+        return self._shadow, fresh
+
+
+def _load_features(module: nn.Module, state_dict, what: str) -> int:
+    """copy every ``features.*`` entry of ``state_dict`` into the parameter or buffer of that name; all or nothing"""
+    own = dict(module.named_parameters())
+    own.update(dict(module.named_buffers()))
+    todo = []
+    for key, src in state_dict.items():
+        if not key.startswith("features."):
+            continue
+        dst = own.get(key)
+        if dst is None:
+            raise KeyError(f"load_pretrained: {key} is not a parameter or buffer of {what}")
+        if tuple(dst.shape) != tuple(src.shape):
+            raise ValueError(f"load_pretrained: {key} has shape {tuple(src.shape)} in the checkpoint, the backbone expects {tuple(dst.shape)}")
+        todo.append((dst, src))
+    for dst, src in todo:          # nothing is copied unless everything fits
+        dst.copy_(src)
+    return len(todo)
 
 
 class YOLOv1Backbone(_PlanOwner, Backbone):
@@ -92,8 +166,12 @@ class YOLOv1Backbone(_PlanOwner, Backbone):
     Layer list = src/yolo/models.py:47-84 of the reference (indices inside ``features`` are part of
     the checkpoint contract)."""
 
-    def __init__(self):
+    def __init__(self, batch_norm: bool = False):
         super().__init__()
+        self.batch_norm = bool(batch_norm)
+        if self.batch_norm:
+            self._init_bn()
+            return
         mods: list[nn.Module] = []
         mods += _conv_act(3, 64, 7, 2, 3) + [nn.MaxPool2d(2, 2)]
         mods += _conv_act(64, 192, 3, 1, 1) + [nn.MaxPool2d(2, 2)]
@@ -106,15 +184,38 @@ class YOLOv1Backbone(_PlanOwner, Backbone):
         self.features = nn.Sequential(*mods)
         self._plan: engine.Plan | None = None
 
-    def _make_conv_block(self, in_channels: int, mid_channels: int, out_channels: int, num_blocks: int) -> list[nn.Module]:
+    def _init_bn(self):
+        """the same 24 convolutions with ``Conv2d(bias=False), BatchNorm2d, LeakyReLU(0.1)`` in place of ``Conv2d, LeakyReLU(0.1)`` (Darknet's
+        yolov1.cfg: batch_normalize=1 on every convolution); the pools stay where they are.  Extension of the reference surface."""
+        ca = lambda *a: _conv_act(*a, bn=True)      # noqa: E731
+        mods: list[nn.Module] = []
+        mods += ca(3, 64, 7, 2, 3) + [nn.MaxPool2d(2, 2)]
+        mods += ca(64, 192, 3, 1, 1) + [nn.MaxPool2d(2, 2)]
+        mods += ca(192, 128, 1) + ca(128, 256, 3, 1, 1) + ca(256, 256, 1) + ca(256, 512, 3, 1, 1) + [nn.MaxPool2d(2, 2)]
+        mods += self._make_conv_block(512, 256, 512, 4, True)
+        mods += ca(512, 512, 1) + ca(512, 1024, 3, 1, 1) + [nn.MaxPool2d(2, 2)]
+        mods += self._make_conv_block(1024, 512, 1024, 2, True)
+        mods += ca(1024, 1024, 3, 1, 1) + ca(1024, 1024, 3, 2, 1)
+        mods += ca(1024, 1024, 3, 1, 1) + ca(1024, 1024, 3, 1, 1)
+        self.features = nn.Sequential(*mods)
+        self._plan = None
+        self._bn = _BNFeatures(self.features)
+
+    def _make_conv_block(self, in_channels: int, mid_channels: int, out_channels: int, num_blocks: int, bn: bool = False) -> list[nn.Module]:
         """``num_blocks`` x [1x1 reduce -> 3x3 expand], each followed by LeakyReLU(0.1)."""
         out: list[nn.Module] = []
         for _ in range(num_blocks):
-            out += _conv_act(in_channels, mid_channels, 1) + _conv_act(mid_channels, out_channels, 3, 1, 1)
+            out += _conv_act(in_channels, mid_channels, 1, bn=bn) + _conv_act(mid_channels, out_channels, 3, 1, 1, bn=bn)
             in_channels = out_channels
         return out
 
     def hip_plan(self) -> engine.Plan:
+        """the plan of the plain stack; with batch_norm=True, of the stack with its BatchNorm layers folded in (inference)"""
+        if self.batch_norm:
+            mods, fresh = self._bn.folded()
+            if self._plan is None or fresh:
+                self._plan = engine.Plan.from_modules(mods, 3, True)
+            return self._own(self._plan)
         if self._plan is None:
             self._plan = engine.Plan.from_modules(self.features, 3, True)
         return self._own(self._plan)
@@ -125,25 +226,18 @@ class YOLOv1Backbone(_PlanOwner, Backbone):
         ``features.N.weight`` / ``features.N.bias`` of ``state_dict`` is copied into layer N of this backbone; its other entries (the classifier's
         ``fc.*``) are ignored, and the layers the checkpoint does not hold -- the four convolutions detection adds -- stay as initialised.
         A tensor of another shape, or a layer this backbone does not have, raises naming the key.  Returns the number of tensors loaded
-        (40 for the paper's 20 convolutions).  Extension of the reference surface, which pretrains nothing."""
-        own = dict(self.named_parameters())
-        todo = []
-        for key, src in state_dict.items():
-            if not key.startswith("features."):
-                continue
-            dst = own.get(key)
-            if dst is None:
-                raise KeyError(f"load_pretrained: {key} is not a parameter of YOLOv1Backbone")
-            if tuple(dst.shape) != tuple(src.shape):
-                raise ValueError(f"load_pretrained: {key} has shape {tuple(src.shape)} in the checkpoint, the backbone expects {tuple(dst.shape)}")
-            todo.append((dst, src))
-        for dst, src in todo:          # nothing is copied unless everything fits
-            dst.copy_(src)
-        return len(todo)
+        (40 for the paper's 20 convolutions; 120 with batch_norm=True: 20 conv weights + 20 x (weight, bias, running_mean, running_var,
+        num_batches_tracked)).  A plain checkpoint into a BatchNorm backbone, or the reverse, raises naming the first key that does not fit.
+        Extension of the reference surface, which pretrains nothing."""
+        return _load_features(self, state_dict, f"YOLOv1Backbone(batch_norm={self.batch_norm})")
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if x.is_cuda:
-            return engine.run_plan(self.hip_plan(), x, self.training)
+            if self.batch_norm and self._bn.wants_train_path(self.training):
+                return engine.run_bn_plan(self._bn.train_plan(), x, self.training)
+            return engine.run_plan(self.hip_plan(), x, self.training and not self.batch_norm)
+        if not isinstance(x, torch.Tensor):
+            x = x.to_tensor()
         return self.features(x)
 
 
@@ -248,17 +342,44 @@ class YOLOv1(_PlanOwner, nn.Module):
                 raise ValueError("Must provide detection_head for custom backbone types")
         self.head = detection_head
         self._plan: engine.Plan | None = None
+        self._head_plan: engine.Plan | None = None
 
-    def _fusable(self) -> bool:
+    def _default_pair(self) -> bool:
         h = self.head
         return (type(self.backbone) is YOLOv1Backbone and type(h) is nn.Sequential and len(h) == 5
                 and isinstance(h[0], nn.Flatten) and isinstance(h[1], nn.Linear) and isinstance(h[2], nn.LeakyReLU)
                 and isinstance(h[3], nn.Dropout) and isinstance(h[4], nn.Linear))
 
+    def _bn_backbone(self) -> bool:
+        return type(self.backbone) is YOLOv1Backbone and self.backbone.batch_norm
+
+    def _fusable(self) -> bool:
+        """backbone and head as ONE plan: the default pair -- with a BatchNorm backbone only where its BatchNorm layers fold (no training path)"""
+        return self._default_pair() and not (self.backbone.batch_norm and self.backbone._bn.wants_train_path(self.backbone.training))
+
     def hip_plan(self) -> engine.Plan:
+        if self._bn_backbone():
+            mods, fresh = self.backbone._bn.folded()
+            if self._plan is None or fresh:
+                self._plan = engine.Plan.from_modules(list(mods) + list(self.head), 3, True)
+            return self._own(self._plan)
         if self._plan is None:
             self._plan = engine.Plan.from_modules(list(self.backbone.features) + list(self.head), 3, True)
         return self._own(self._plan)
+
+    def head_plan(self) -> engine.Plan:
+        """BatchNorm backbone with gradients: the default head as a plan of its own behind the BatchNorm chain (never stock device ops)"""
+        if self._head_plan is None:
+            self._head_plan = engine.Plan.from_modules(list(self.head), 1024, False)
+        return self._own(self._head_plan)
+
+    def hip_plans(self) -> list:
+        """the plans whose parameters a training step of this model updates, in forward order (``yolo.optim.GradAccumulator``,
+        ``parallel.make_grad_reducer``): the fused plan, or -- BatchNorm backbone -- the head's; the backbone's parameters then travel through
+        autograd like the ResNet trunk's"""
+        if self._bn_backbone() and self._default_pair():
+            return [self.head_plan()]
+        return [self.hip_plan()] if self._default_pair() else []
 
     @torch.no_grad()
     def forward_uint8(self, images: torch.Tensor, size: tuple[int, int] = (448, 448)) -> torch.Tensor:
@@ -275,6 +396,8 @@ class YOLOv1(_PlanOwner, nn.Module):
         YOLOv1 augments it straight into the stem's input buffer, every other model takes its fp32 tensor (``U8Batch.to_tensor``)."""
         if x.is_cuda and self._fusable():
             y = engine.run_plan(self.hip_plan(), x, self.training)
+        elif x.is_cuda and self._bn_backbone() and self._default_pair():
+            y = engine.run_plan(self.head_plan(), self.backbone(x), self.training)
         else:
             if not isinstance(x, torch.Tensor):
                 x = x.to_tensor()

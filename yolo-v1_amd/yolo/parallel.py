@@ -201,7 +201,7 @@ def make_grad_reducer(model: torch.nn.Module, device, group=None):
         head_ids = {id(p) for p in head.parameters()}
         rest = [p for p in model.parameters() if id(p) not in head_ids]
         return _Both(OverlappedGradAllReduce(head.hip_plan(), device, group=group), GradAllReduce(rest, group=group))
-    if on_gpu and hasattr(model, "hip_plans"):
+    if on_gpu and hasattr(model, "hip_plans") and model.hip_plans():
         plans = list(reversed(model.hip_plans()))
         covered = {id(p) for plan in plans for p in plan.params}
         rest = [p for p in model.parameters() if id(p) not in covered]

@@ -16,9 +16,200 @@ from .plans import igemm_call
 from .runtime import RT, Act, _igemm, _on_side_stream, _round_up, _timed, desc_aux, igemm_desc, stem_tiles_ok
 
 # ====================================================================================================
+# what the conv -> BatchNorm executors share (ResNetPlan below, bn_executor.BNPlan): buffers, conv descriptors, the stem, and the
+# weight-gradient / data-gradient launches of a backward pass
+# ====================================================================================================
+class _ConvBNBase:
+    # -- BN folding: y = gamma * (conv(x) - mean) / sqrt(var + eps) + beta
+    @staticmethod
+    def _fold(conv: nn.Conv2d, bn: nn.BatchNorm2d):
+        scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
+        w = conv.weight.detach().float() * scale.view(-1, 1, 1, 1)
+        b = bn.bias.detach().float() - bn.running_mean.detach().float() * scale
+        if conv.bias is not None:
+            b = b + conv.bias.detach().float() * scale
+        return w.contiguous(), b.contiguous()
+
+
+    def _scratch(self, dev):
+        if self._bn_scratch is None or self._bn_scratch[0].device != dev:
+            self._bn_scratch = (torch.zeros(_hip.BN_ACC_REPLICAS * 2 * 2048, dtype=torch.float64, device=dev), torch.empty(2 * 2048, dtype=torch.float32, device=dev))
+        return self._bn_scratch
+
+    def _bwd_scratch(self, dev):
+        if getattr(self, "_coef", None) is None or self._coef.device != dev:
+            self._coef = torch.empty(3 * 2048, dtype=torch.float32, device=dev)
+            self._zero_bias = torch.zeros(2048, dtype=torch.float32, device=dev)
+
+    def _act(self, key, N, H, W, C, halo, dev):
+        k = (key, N, H, W, C, halo, str(dev))
+        a = self._bufs.get(k)
+        if a is None:
+            a = Act(N, H, W, C, halo, dev)
+            self._bufs[k] = a
+        return a
+
+    @staticmethod
+    def _geom(a_in: Act, conv: nn.Conv2d):
+        """(k, stride, pad, Ho, Wo) of conv over a_in"""
+        k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
+        return k, s, p, (a_in.H + 2 * p - k) // s + 1, (a_in.W + 2 * p - k) // s + 1
+
+    @staticmethod
+    def _desc(a_in: Act, shift: int, stride: int, k: int, a_out: Act, epilogue: int, slope: float) -> IgemmDesc:
+        """a k x k conv that reads a_in from `shift` pixels up / left of its interior and fills a_out's interior, channels as the buffers have them"""
+        d = igemm_desc(a_out.N, a_out.H, a_out.W, stride, k, k, a_in.C, a_out.C, a_in, a_in.interior_off(shift), a_out)
+        d.epilogue, d.slope = epilogue, slope
+        return d
+
+    def _stem_input(self, x: torch.Tensor, st):
+        """the batch as the stem reads it -> (NHWC4 bf16 copy with a halo of 3, output height, output width of the 7x7/s2/p3 conv)"""
+        N, _, H, W = x.shape
+        x = x.detach()
+        if x.dtype != torch.float32 or not x.is_contiguous():
+            x = x.float().contiguous()
+        a = self._act("in", N, H, W, 4, 3, x.device)
+        check(RT.lib().yolo_nchw_f32_to_nhwc_bf16(ptr(x), N, 3, H, W, a.p, 4, 3, 3, st), "nchw->nhwc4")
+        return a, (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
+
+    @staticmethod
+    def _stem_desc(a: Act, out: Act, epilogue: int, slope: float) -> IgemmDesc:
+        """the stem as a row-segment implicit GEMM: 7 taps of 8 pixels x 4 channels per output pixel"""
+        d = igemm_desc(a.N, out.H, out.W, 2, 7, 1, 32, 64, a, 0, out)
+        d.epilogue, d.slope = epilogue, slope
+        return d
+
+    @staticmethod
+    def _to_nchw(cur: Act, dev, st) -> torch.Tensor:
+        out = torch.empty((cur.N, cur.C, cur.H, cur.W), dtype=torch.float32, device=dev)
+        check(RT.lib().yolo_nhwc_bf16_to_nchw_f32(cur.p, cur.N, cur.C, cur.H, cur.W, cur.halo, ptr(out), st), "nhwc->nchw")
+        return out
+
+    def _pack_train_units(self, units):
+        """units: (name, conv, bn, first) in forward order -> {name: (forward operand, data-gradient operand, conv, bn)}, cached on the weights' versions"""
+        ver = tuple(int(conv.weight._version) for (_, conv, _, _) in units)
+        if getattr(self, "_train_pk", None) is not None and self._train_pk[0] == ver:
+            return self._train_pk[1]
+        st = RT.stream()
+        out = self._train_pk[1] if getattr(self, "_train_pk", None) is not None else {}
+        items = []
+        for (name, conv, bn, first) in units:
+            w = conv.weight.detach()
+            if w.dtype != torch.float32 or not w.is_contiguous():
+                w = w.float().contiguous()
+            co, ci, k, _ = w.shape
+            if name in out and out[name][0].device == w.device:
+                wf, wd = out[name][0], out[name][1]
+            elif first:
+                wf, wd = torch.empty((co, 7, 8, 4), dtype=torch.bfloat16, device=w.device), None
+            else:
+                wf = torch.empty((co, k, k, ci), dtype=torch.bfloat16, device=w.device)
+                wd = torch.empty((ci, k, k, co), dtype=torch.bfloat16, device=w.device)
+            if first:
+                check(RT.lib().yolo_pack_conv_weight(ptr(w), co, 3, 7, 7, 4, 8, ptr(wf), None, st), "pack stem")
+            elif co % 64 == 0 and ci % 64 == 0:
+                items.append((ConvPackItem(w.data_ptr(), wf.data_ptr(), wd.data_ptr(), co, ci, k, k), w))
+            else:
+                check(RT.lib().yolo_pack_conv_weight(ptr(w), co, ci, k, k, ci, k, ptr(wf), ptr(wd), st), "pack")
+            out[name] = (wf, wd, conv, bn)
+        for i in range(0, len(items), 32):
+            tab = (ConvPackItem * len(items[i: i + 32]))(*[it[0] for it in items[i: i + 32]])
+            check(RT.lib().yolo_pack_conv_weights_multi(tab, len(items[i: i + 32]), st), "pack_conv_weights_multi")
+        self._train_pk = (ver, out)
+        return out
+
+    def _stem_wgrad(self, xin: Act, dz0: Act, conv: nn.Conv2d, N, Ho, Wo, dev, st) -> torch.Tensor:
+        """fp32 weight gradient of the 7x7/s2 stem from its NHWC4 input and dz0 (Ho x Wo, 64 channels): the direct kernel, or the row-unfolded fallback"""
+        L_ = RT.lib()
+        dw = torch.empty_like(conv.weight, dtype=torch.float32)
+        part = getattr(self, "_stem_part", None)
+        if part is None or part.device != dev:
+            part = self._stem_part = torch.empty((768 * 14400,), dtype=torch.float32, device=dev)
+            self._stem_db = torch.empty(64, dtype=torch.float32, device=dev)
+        if stem_tiles_ok(64, Ho, Wo):
+            check(L_.yolo_wgrad_stem7(xin.p, dz0.p, N, Ho, Wo, xin.img_stride, xin.row_stride, dz0.img_stride, dz0.row_stride, dz0.interior_off(),
+                                      ptr(dw), ptr(self._stem_db), ptr(part), part.numel(), st), "wgrad_stem7")
+        else:
+            # stem maps that the direct kernel's 8 x 16-pixel tiles do not cover (inputs that are not (16k) x (32k) pixels): the generic weight-gradient
+            # kernel over a row-unfolded copy of the input (7 kernel rows x 8 columns x 4 channels per output pixel), as Plan.backward does
+            xcol = self._act(("stem", "xcol"), N, Ho, Wo, 7 * 32, 1, dev)
+            check(L_.yolo_im2col_rows(xin.p, xin.img_stride, xin.row_stride, xin.px_stride, 2, 7, 32, N, Ho, Wo, 1, xcol.p, st), "im2col_rows")
+            dwp = torch.zeros(64 * 7 * 8 * 4, dtype=torch.float32, device=dev)
+            wd = WgradDesc(dz0.slots, dz0.px_stride, xcol.px_stride, 64, 7 * 32, 1, 1, 0, xcol.row_stride, max(1, min(1024, dz0.slots // 4096)), 0)
+            check(L_.yolo_wgrad(ctypes.byref(wd), xcol.p, dz0.p, ptr(dwp), None, st), "wgrad stem")
+            check(L_.yolo_unpack_conv_wgrad(ptr(dwp), 64, 3, 7, 7, 4, 8, ptr(dw), 0, st), "unpack stem")
+        return dw
+
+
+class _TrainBackward:
+    """one backward pass over conv -> BatchNorm units: the weight gradients (and their unpack passes) on the low-priority second stream, beside the
+    BatchNorm-backward / data-gradient chain (Plan.backward does the same): the chain's HBM-bound BatchNorm passes and the MFMA-bound weight gradients
+    mix well.  ``grads`` collects {parameter: fp32 gradient}."""
+
+    def __init__(self, plan: _ConvBNBase, convs, N, dev, st):
+        self.plan, self.N, self.dev, self.st = plan, N, dev, st
+        self.L_ = RT.lib()
+        self.grads: dict = {}
+        self.offs, tot = {}, 0
+        for c in convs:
+            self.offs[id(c)] = tot
+            tot += _round_up(c.weight.numel(), 64)
+        self.scratch = torch.zeros(tot, dtype=torch.float32, device=dev)
+        self.pending: list = []
+        self.main_t = torch.cuda.current_stream(dev)
+        self.side_t = Plan._side_stream(dev) if CFG.WGRAD_STREAM else None
+
+    def flush(self):
+        with _on_side_stream(self.main_t, self.side_t):
+            pending = self.pending
+            for i in range(0, len(pending), 32):
+                items = [ConvUnpackItem(dwp.data_ptr(), dw.data_ptr(), c.out_channels, c.in_channels, c.kernel_size[0], c.kernel_size[1])
+                         for (c, dwp, dw) in pending[i: i + 32]]
+                check(self.L_.yolo_unpack_conv_wgrads_multi((ConvUnpackItem * len(items))(*items), len(items), RT.stream()), "unpack_conv_wgrads_multi")
+            pending.clear()
+
+    def wgrad(self, u, dz: Act):
+        N = self.N
+        conv, xin, k, s, p = u["conv"], u["x"], u["k"], u["s"], u["p"]
+        Hout, Wout = u["z"].H, u["z"].W
+        o = self.offs[id(conv)]
+        dwp = self.scratch[o: o + conv.weight.numel()]
+        if Hout >= 2 and Wout >= 2 and (s > 1 or dz.Hp * dz.Wp >= 1.12 * Hout * Wout):
+            wd = WgradDesc(N * Hout * Wout, dz.px_stride, xin.px_stride, conv.out_channels, conv.in_channels, k, k, p, xin.row_stride, 0, 0, 0,
+                           Wout, Hout, dz.Hp * dz.Wp, dz.Wp * s, s, dz.halo * dz.Wp + dz.halo)
+        else:
+            wd = WgradDesc(dz.slots, dz.px_stride, xin.px_stride, conv.out_channels, conv.in_channels, k, k, p, xin.row_stride, 0, 0)
+        dw = torch.empty_like(conv.weight, dtype=torch.float32)
+        with _on_side_stream(self.main_t, self.side_t) as wst:
+            with _timed(f"{u['tag']}.wgrad", "wgrad", 2.0 * N * Hout * Wout * conv.out_channels * conv.in_channels * k * k):
+                check(self.L_.yolo_wgrad(ctypes.byref(wd), xin.p, dz.p, ptr(dwp), None, wst), f"wgrad {u['tag']}")
+        self.grads[conv.weight] = dw
+        self.pending.append((conv, dwp, dw))
+
+    def dgrad(self, u, dz: Act, add: Act | None) -> Act:
+        N, plan = self.N, self.plan
+        conv, xin, k, p = u["conv"], u["x"], u["k"], u["p"]
+        g = plan._act((u["tag"], "gx"), N, xin.H, xin.W, conv.in_channels, 1, self.dev)
+        d = plan._desc(dz, k - 1 - p, 1, k, g, EPI_NONE, 1.0)         # over the conv's input grid, with the flipped panel
+        d.split_k = 1
+        aux, bias = None, None
+        if add is not None:
+            d.epilogue = _hip.EPI_BIAS_ADD_LRELU          # slope 1: out = conv + 0 + aux
+            desc_aux(d, add)
+            aux, bias = add.p, ptr(plan._zero_bias)
+        with _timed(f"{u['tag']}.dgrad", "igemm", 2.0 * N * xin.H * xin.W * conv.out_channels * conv.in_channels * k * k):
+            igemm_call(d, dz.p, ptr(u["wd"]), bias, aux, g.p, self.st, f"dgrad {u['tag']}")
+        return g
+
+    def finish(self):
+        if self.side_t is not None:
+            self.main_t.wait_stream(self.side_t)
+
+
+# ====================================================================================================
 # ResNet-50 trunk, inference only (BatchNorm folded into the conv that precedes it)
 # ====================================================================================================
-class ResNetPlan:
+class ResNetPlan(_ConvBNBase):
     """Inference executor for ``yolo.resnet.resnet50_trunk`` on the same kernels: every conv+BN(+ReLU) is
     one yolo_igemm (BN folded into the bf16 weights and an fp32 bias at pack time), the residual add + ReLU
     of a bottleneck is the epilogue of its last 1x1 conv (YOLO_EPI_BIAS_ADD_LRELU with slope 0), the stem's
@@ -33,16 +224,6 @@ class ResNetPlan:
         self._bn_scratch = None
         self._bufs: dict = {}
         self.trace = None            # tests: a list that backward_train fills with per-block gradients
-
-    # -- BN folding: y = gamma * (conv(x) - mean) / sqrt(var + eps) + beta
-    @staticmethod
-    def _fold(conv: nn.Conv2d, bn: nn.BatchNorm2d):
-        scale = bn.weight.detach().float() / torch.sqrt(bn.running_var.detach().float() + bn.eps)
-        w = conv.weight.detach().float() * scale.view(-1, 1, 1, 1)
-        b = bn.bias.detach().float() - bn.running_mean.detach().float() * scale
-        if conv.bias is not None:
-            b = b + conv.bias.detach().float() * scale
-        return w.contiguous(), b.contiguous()
 
     def _pack_all(self):
         ver = tuple(int(p._version) for p in self.trunk.parameters()) + tuple(int(b._version) for b in self.trunk.buffers())
@@ -120,11 +301,6 @@ class ResNetPlan:
         if not frozen:
             bn.num_batches_tracked += 1
 
-    def _scratch(self, dev):
-        if self._bn_scratch is None or self._bn_scratch[0].device != dev:
-            self._bn_scratch = (torch.zeros(_hip.BN_ACC_REPLICAS * 2 * 2048, dtype=torch.float64, device=dev), torch.empty(2 * 2048, dtype=torch.float32, device=dev))
-        return self._bn_scratch
-
     def _conv_bn_train(self, tag, a_in: Act, packed, N, relu: bool, residual: Act | None, dev, st):
         wf, _, conv, bn = packed
         k, s, p, Ho, Wo = self._geom(a_in, conv)
@@ -162,46 +338,13 @@ class ResNetPlan:
     def _pack_train(self):
         """bf16 forward AND data-gradient operands of the raw conv weights (the stem needs no data gradient); refreshed with
         yolo_pack_conv_weights_multi, 32 layers per launch, whenever a weight changed"""
-        ver = tuple(int(p._version) for n, p in self.trunk.named_parameters() if p.dim() == 4)
-        if getattr(self, "_train_pk", None) is not None and self._train_pk[0] == ver:
-            return self._train_pk[1]
-        st = RT.stream()
-        out = self._train_pk[1] if getattr(self, "_train_pk", None) is not None else {}
-        items = []
-
-        def pack(name, conv, bn, first=False):
-            w = conv.weight.detach()
-            if w.dtype != torch.float32 or not w.is_contiguous():
-                w = w.float().contiguous()
-            co, ci, k, _ = w.shape
-            if name in out:
-                wf, wd = out[name][0], out[name][1]
-            elif first:
-                wf, wd = torch.empty((co, 7, 8, 4), dtype=torch.bfloat16, device=w.device), None
-            else:
-                wf = torch.empty((co, k, k, ci), dtype=torch.bfloat16, device=w.device)
-                wd = torch.empty((ci, k, k, co), dtype=torch.bfloat16, device=w.device)
-            if first:
-                check(RT.lib().yolo_pack_conv_weight(ptr(w), co, 3, 7, 7, 4, 8, ptr(wf), None, st), "pack stem")
-            elif co % 64 == 0 and ci % 64 == 0:
-                items.append((ConvPackItem(w.data_ptr(), wf.data_ptr(), wd.data_ptr(), co, ci, k, k), w))
-            else:
-                check(RT.lib().yolo_pack_conv_weight(ptr(w), co, ci, k, k, ci, k, ptr(wf), ptr(wd), st), "pack")
-            out[name] = (wf, wd, conv, bn)
-
-        pack("stem", self.trunk[0], self.trunk[1], first=True)
+        units = [("stem", self.trunk[0], self.trunk[1], True)]
         for li in range(4, 8):
             for bi, blk in enumerate(self.trunk[li]):
-                pack((li, bi, 1), blk.conv1, blk.bn1)
-                pack((li, bi, 2), blk.conv2, blk.bn2)
-                pack((li, bi, 3), blk.conv3, blk.bn3)
+                units += [((li, bi, 1), blk.conv1, blk.bn1, False), ((li, bi, 2), blk.conv2, blk.bn2, False), ((li, bi, 3), blk.conv3, blk.bn3, False)]
                 if blk.downsample is not None:
-                    pack((li, bi, "d"), blk.downsample[0], blk.downsample[1])
-        for i in range(0, len(items), 32):
-            tab = (ConvPackItem * len(items[i: i + 32]))(*[it[0] for it in items[i: i + 32]])
-            check(RT.lib().yolo_pack_conv_weights_multi(tab, len(items[i: i + 32]), st), "pack_conv_weights_multi")
-        self._train_pk = (ver, out)
-        return out
+                    units.append(((li, bi, "d"), blk.downsample[0], blk.downsample[1], False))
+        return self._pack_train_units(units)
 
     def _unit_fwd(self, tag, a_in: Act, packed, N, relu: bool, residual: Act | None, stats: torch.Tensor, dev, st, frozen: bool = False):
         """conv -> z (kept) -> BatchNorm(batch statistics; frozen: running statistics) [+ residual] [ReLU] -> y; returns the record the backward needs."""
@@ -273,32 +416,10 @@ class ResNetPlan:
             raise RuntimeError("ResNetPlan: a later training forward has reused this forward's activation buffers -- call backward() "
                                "before the next forward of the same backbone (one forward in flight per plan)")
         acc, _ = self._bn_scratch
-        if getattr(self, "_coef", None) is None or self._coef.device != dev:
-            self._coef = torch.empty(3 * 2048, dtype=torch.float32, device=dev)
-            self._zero_bias = torch.zeros(2048, dtype=torch.float32, device=dev)
-        grads: dict = {}
+        self._bwd_scratch(dev)
         convs = [u["conv"] for b in saved["blocks"] for u in b[2:] if u is not None]
-        offs, tot = {}, 0
-        for c in convs:
-            offs[id(c)] = tot
-            tot += _round_up(c.weight.numel(), 64)
-        scratch = torch.zeros(tot, dtype=torch.float32, device=dev)
-        pending = []
-        # weight gradients (and their unpack passes) on the low-priority second stream, beside the BatchNorm-backward / data-gradient
-        # chain (Plan.backward does the same): the chain's HBM-bound BatchNorm passes and the MFMA-bound weight gradients mix well
-        main_t = torch.cuda.current_stream(dev)
-        side_t = Plan._side_stream(dev) if CFG.WGRAD_STREAM else None
-
-        def flush():
-            with _on_side_stream(main_t, side_t):
-                _flush()
-
-        def _flush():
-            for i in range(0, len(pending), 32):
-                items = [ConvUnpackItem(dwp.data_ptr(), dw.data_ptr(), c.out_channels, c.in_channels, c.kernel_size[0], c.kernel_size[1])
-                         for (c, dwp, dw) in pending[i: i + 32]]
-                check(L_.yolo_unpack_conv_wgrads_multi((ConvUnpackItem * len(items))(*items), len(items), RT.stream()), "unpack_conv_wgrads_multi")
-            pending.clear()
+        B = _TrainBackward(self, convs, N, dev, st)
+        grads, pending, flush, wgrad, dgrad = B.grads, B.pending, B.flush, B.wgrad, B.dgrad
 
         def bn_bwd(u, dy: Act, store_masked: bool) -> Act:
             """dz of unit u from the gradient dy wrt its output, in the geometry of the conv's INPUT grid (zero-stuffed for stride 2)"""
@@ -320,37 +441,6 @@ class ResNetPlan:
                   f"batchnorm_bwd {u['tag']}")
             grads[bn.weight], grads[bn.bias] = dg, db
             return dz
-
-        def wgrad(u, dz: Act):
-            conv, xin, k, s, p = u["conv"], u["x"], u["k"], u["s"], u["p"]
-            Hout, Wout = u["z"].H, u["z"].W
-            o = offs[id(conv)]
-            dwp = scratch[o: o + conv.weight.numel()]
-            if Hout >= 2 and Wout >= 2 and (s > 1 or dz.Hp * dz.Wp >= 1.12 * Hout * Wout):
-                wd = WgradDesc(N * Hout * Wout, dz.px_stride, xin.px_stride, conv.out_channels, conv.in_channels, k, k, p, xin.row_stride, 0, 0, 0,
-                               Wout, Hout, dz.Hp * dz.Wp, dz.Wp * s, s, dz.halo * dz.Wp + dz.halo)
-            else:
-                wd = WgradDesc(dz.slots, dz.px_stride, xin.px_stride, conv.out_channels, conv.in_channels, k, k, p, xin.row_stride, 0, 0)
-            dw = torch.empty_like(conv.weight, dtype=torch.float32)
-            with _on_side_stream(main_t, side_t) as wst:
-                with _timed(f"{u['tag']}.wgrad", "wgrad", 2.0 * N * Hout * Wout * conv.out_channels * conv.in_channels * k * k):
-                    check(L_.yolo_wgrad(ctypes.byref(wd), xin.p, dz.p, ptr(dwp), None, wst), f"wgrad {u['tag']}")
-            grads[conv.weight] = dw
-            pending.append((conv, dwp, dw))
-
-        def dgrad(u, dz: Act, add: Act | None) -> Act:
-            conv, xin, k, p = u["conv"], u["x"], u["k"], u["p"]
-            g = self._act((u["tag"], "gx"), N, xin.H, xin.W, conv.in_channels, 1, dev)
-            d = self._desc(dz, k - 1 - p, 1, k, g, EPI_NONE, 1.0)         # over the conv's input grid, with the flipped panel
-            d.split_k = 1
-            aux, bias = None, None
-            if add is not None:
-                d.epilogue = _hip.EPI_BIAS_ADD_LRELU          # slope 1: out = conv + 0 + aux
-                desc_aux(d, add)
-                aux, bias = add.p, ptr(self._zero_bias)
-            with _timed(f"{u['tag']}.dgrad", "igemm", 2.0 * N * xin.H * xin.W * conv.out_channels * conv.in_channels * k * k):
-                igemm_call(d, dz.p, ptr(u["wd"]), bias, aux, g.p, st, f"dgrad {u['tag']}")
-            return g
 
         out = saved["out"]
         gout = gout.detach()
@@ -389,66 +479,10 @@ class ResNetPlan:
         check(L_.yolo_maxpool3s2_bwd(ctypes.byref(pd), y0.p, cur_g.p, g_y0.p, g_y0.halo, st), "maxpool3s2_bwd")
         dz0 = bn_bwd(stem, g_y0, False)
         conv = stem["conv"]
-        dw = torch.empty_like(conv.weight, dtype=torch.float32)
-        part = getattr(self, "_stem_part", None)
-        if part is None or part.device != dev:
-            part = self._stem_part = torch.empty((768 * 14400,), dtype=torch.float32, device=dev)
-            self._stem_db = torch.empty(64, dtype=torch.float32, device=dev)
-        if stem_tiles_ok(64, y0.H, y0.W):
-            check(L_.yolo_wgrad_stem7(xin.p, dz0.p, N, y0.H, y0.W, xin.img_stride, xin.row_stride, dz0.img_stride, dz0.row_stride, dz0.interior_off(),
-                                      ptr(dw), ptr(self._stem_db), ptr(part), part.numel(), st), "wgrad_stem7")
-        else:
-            # stem maps that the direct kernel's 8 x 16-pixel tiles do not cover (inputs that are not (16k) x (32k) pixels): the generic weight-gradient
-            # kernel over a row-unfolded copy of the input (7 kernel rows x 8 columns x 4 channels per output pixel), as Plan.backward does
-            xcol = self._act(("stem", "xcol"), N, y0.H, y0.W, 7 * 32, 1, dev)
-            check(L_.yolo_im2col_rows(xin.p, xin.img_stride, xin.row_stride, xin.px_stride, 2, 7, 32, N, y0.H, y0.W, 1, xcol.p, st), "im2col_rows")
-            dwp = torch.zeros(64 * 7 * 8 * 4, dtype=torch.float32, device=dev)
-            wd = WgradDesc(dz0.slots, dz0.px_stride, xcol.px_stride, 64, 7 * 32, 1, 1, 0, xcol.row_stride, max(1, min(1024, dz0.slots // 4096)), 0)
-            check(L_.yolo_wgrad(ctypes.byref(wd), xcol.p, dz0.p, ptr(dwp), None, st), "wgrad stem")
-            check(L_.yolo_unpack_conv_wgrad(ptr(dwp), 64, 3, 7, 7, 4, 8, ptr(dw), 0, st), "unpack stem")
+        dw = self._stem_wgrad(xin, dz0, conv, N, y0.H, y0.W, dev, st)
         grads[conv.weight] = dw
-        if side_t is not None:
-            main_t.wait_stream(side_t)          # every weight gradient is final before the pass returns
+        B.finish()          # every weight gradient is final before the pass returns
         return grads
-
-    def _act(self, key, N, H, W, C, halo, dev):
-        k = (key, N, H, W, C, halo, str(dev))
-        a = self._bufs.get(k)
-        if a is None:
-            a = Act(N, H, W, C, halo, dev)
-            self._bufs[k] = a
-        return a
-
-    # ------------------------------------------------------------------ what the three forwards and the backward share
-    @staticmethod
-    def _geom(a_in: Act, conv: nn.Conv2d):
-        """(k, stride, pad, Ho, Wo) of conv over a_in"""
-        k, s, p = conv.kernel_size[0], conv.stride[0], conv.padding[0]
-        return k, s, p, (a_in.H + 2 * p - k) // s + 1, (a_in.W + 2 * p - k) // s + 1
-
-    @staticmethod
-    def _desc(a_in: Act, shift: int, stride: int, k: int, a_out: Act, epilogue: int, slope: float) -> IgemmDesc:
-        """a k x k conv that reads a_in from `shift` pixels up / left of its interior and fills a_out's interior, channels as the buffers have them"""
-        d = igemm_desc(a_out.N, a_out.H, a_out.W, stride, k, k, a_in.C, a_out.C, a_in, a_in.interior_off(shift), a_out)
-        d.epilogue, d.slope = epilogue, slope
-        return d
-
-    def _stem_input(self, x: torch.Tensor, st):
-        """the batch as the stem reads it -> (NHWC4 bf16 copy with a halo of 3, output height, output width of the 7x7/s2/p3 conv)"""
-        N, _, H, W = x.shape
-        x = x.detach()
-        if x.dtype != torch.float32 or not x.is_contiguous():
-            x = x.float().contiguous()
-        a = self._act("in", N, H, W, 4, 3, x.device)
-        check(RT.lib().yolo_nchw_f32_to_nhwc_bf16(ptr(x), N, 3, H, W, a.p, 4, 3, 3, st), "nchw->nhwc4")
-        return a, (H + 6 - 7) // 2 + 1, (W + 6 - 7) // 2 + 1
-
-    @staticmethod
-    def _stem_desc(a: Act, out: Act, epilogue: int, slope: float) -> IgemmDesc:
-        """the stem as a row-segment implicit GEMM: 7 taps of 8 pixels x 4 channels per output pixel"""
-        d = igemm_desc(a.N, out.H, out.W, 2, 7, 1, 32, 64, a, 0, out)
-        d.epilogue, d.slope = epilogue, slope
-        return d
 
     def _stem_pool(self, y: Act, dev, st) -> Act:
         """MaxPool2d(3,2,1) behind the stem"""
@@ -456,12 +490,6 @@ class ResNetPlan:
         pd = PoolDesc(y.N, y.H, y.W, 64, 1, 1)
         check(RT.lib().yolo_maxpool3s2_fwd(ctypes.byref(pd), y.p, cur.p, st), "maxpool3s2")
         return cur
-
-    @staticmethod
-    def _to_nchw(cur: Act, dev, st) -> torch.Tensor:
-        out = torch.empty((cur.N, cur.C, cur.H, cur.W), dtype=torch.float32, device=dev)
-        check(RT.lib().yolo_nhwc_bf16_to_nchw_f32(cur.p, cur.N, cur.C, cur.H, cur.W, cur.halo, ptr(out), st), "nhwc->nchw")
-        return out
 
     def _conv(self, tag, a_in: Act, packed, N, relu: bool, residual: Act | None, dev, st):
         wf, b, conv = packed
