@@ -1,4 +1,4 @@
-"""Launch traces of the executors on the CPU: the real ``Plan`` / ``ResNetPlan`` code drives a stand-in library and recording streams (the ``RT``
+"""Launch traces of the executors on the CPU: the real ``Plan`` / ``ResNetPlan`` / ``BNPlan`` code drives a stand-in library and recording streams (the ``RT``
 hooks, as tests/test_parallel_cpu.py does), and every library call and every ``wait_stream`` becomes one normalised line:
 
     entry | scalar arguments | full bytes of every descriptor / array argument | pointers as null / (buffer name, element offset) / tmp
@@ -167,7 +167,7 @@ class Recorder:
         patches = [(RT, "lib", lambda: lib), (RT, "stream", lambda: ctypes.c_void_p(self.cur.cuda_stream)), (RT, "STREAMS", self),
                    (RT, "_SIDE_STREAMS", {}), (RT, "_splitk_scratch", lambda n, zero: torch.zeros(n)),
                    (_hip, "require_cuda", lambda *t: None), (preprocess, "preprocess_u8_into", u8_into),
-                   (torch.cuda, "current_stream", lambda dev=None: self.cur)]      # ResNetPlan.backward_train asks torch for the main stream
+                   (torch.cuda, "current_stream", lambda dev=None: self.cur)]      # (the conv -> BatchNorm executors of a recorded commit may ask torch for the main stream)
         old = [(o, n, getattr(o, n)) for o, n, _ in patches]
         for o, n, v in patches:
             setattr(o, n, v)
@@ -208,7 +208,7 @@ def _model(kind):
         from yolo.resnet import resnet50_trunk
         torch.manual_seed(0)
         _MODELS[kind] = {"yolo": models.YOLOv1, "backbone": models.YOLOv1Backbone, "head": lambda: models.DetectionHead(2048),
-                         "resnet": resnet50_trunk}[kind]()
+                         "resnet": resnet50_trunk, "bn_backbone": lambda: models.YOLOv1Backbone(batch_norm=True)}[kind]()
     return _MODELS[kind]
 
 
@@ -262,7 +262,21 @@ def _infer(N=2, u8=False, **cfg):
     return run
 
 
-def _resnet(mode, size=64):
+@contextlib.contextmanager
+def _switches(sw):
+    """process-wide switches for one scenario (the conv -> BatchNorm executors read ``CONFIG``, not a plan's own copy)"""
+    from yolo.config import CONFIG
+    was = {k: getattr(CONFIG, k) for k in sw}
+    for k, v in sw.items():
+        setattr(CONFIG, k, v)
+    try:
+        yield
+    finally:
+        for k, v in was.items():
+            setattr(CONFIG, k, v)
+
+
+def _resnet(mode, size=64, **sw):
     def run():
         from yolo.resnet_executor import ResNetPlan
         trunk = _model("resnet")
@@ -271,9 +285,11 @@ def _resnet(mode, size=64):
         x = torch.zeros((2, 3, size, size))
         extra = {"x": x}
         try:
-            with rec.recording():
+            with _switches(sw), rec.recording():
                 if mode == "forward":
                     extra["out"] = plan.forward(x)
+                elif mode == "forward_twice":
+                    extra["out"] = [plan.forward(x), plan.forward(x)]
                 elif mode == "batch_stats":
                     extra["out"] = plan.forward_batch_stats(x)
                 else:
@@ -283,6 +299,32 @@ def _resnet(mode, size=64):
                     extra.update(out=out, gout=gout)
         finally:
             trunk.load_state_dict(state)
+        return rec.lines(plan, **extra)
+    return run
+
+
+def _bn(size=448, frozen=False, repack=False, **sw):
+    def run():
+        from yolo.bn_executor import BNPlan
+        feats = _model("bn_backbone").features
+        state = {k: v.clone() for k, v in feats.state_dict().items()}
+        rec, plan = Recorder(), BNPlan.from_modules(feats)
+        x = torch.zeros((2, 3, size, size))
+        extra = {"x": x}
+        try:
+            with _switches(sw), rec.recording():
+                if repack:          # the pack cache: the second forward packs nothing, the third repacks after a weight's version moved
+                    outs = [plan.forward_train(x)[0], plan.forward_train(x)[0]]
+                    with torch.no_grad():
+                        plan.units[3][0].weight.add_(0)
+                    extra["out"] = outs + [plan.forward_train(x)[0]]
+                else:
+                    out, saved = plan.forward_train(x, frozen=frozen)
+                    gout = torch.zeros_like(out)
+                    plan.backward_train(saved, gout)
+                    extra.update(out=out, gout=gout)
+        finally:
+            feats.load_state_dict(state)
         return rec.lines(plan, **extra)
     return run
 
@@ -309,6 +351,16 @@ SCENARIOS = {
     "resnet_train": _resnet("train"),
     "resnet_train_generic_stem": _resnet("train", 48),
     "resnet_train_frozen": _resnet("frozen"),
+    "resnet_forward_twice": _resnet("forward_twice"),                 # the second pass packs nothing
+    "resnet_train_no_BN_STATS_IN_CONV": _resnet("train", BN_STATS_IN_CONV=False),
+    "resnet_batch_stats_no_BN_STATS_IN_CONV": _resnet("batch_stats", BN_STATS_IN_CONV=False),
+    "resnet_train_no_WGRAD_STREAM": _resnet("train", WGRAD_STREAM=False),
+    "bn_train_448": _bn(),
+    "bn_train_240": _bn(240),               # 120 x 120 stem map: im2col stem weight gradient; an odd map: unfused pool forward and backward
+    "bn_train_frozen": _bn(frozen=True),
+    "bn_train_no_BN_POOL_FUSED": _bn(224, BN_POOL_FUSED=False),
+    "bn_train_no_WGRAD_STREAM": _bn(224, WGRAD_STREAM=False),
+    "bn_train_repack": _bn(224, repack=True),
 }
 
 

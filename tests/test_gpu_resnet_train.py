@@ -326,14 +326,14 @@ def test_statistics_from_the_conv_epilogue():
                     for u in (u1, u2, u3, ud):
                         if u is None:
                             continue
-                        z = u["z"].interior().float()
+                        z = u.z.interior().float()
                         C = z.shape[-1]
                         mean = z.mean(dim=(0, 1, 2))
                         var = z.var(dim=(0, 1, 2), unbiased=False)
-                        st = u["stats"]
-                        assert _rel(st[:C], mean) < 1e-4 + 1e-4 * float(mean.abs().max() == 0), (flag, u["tag"], "mean")
-                        assert _rel(st[C:2 * C], torch.rsqrt(var + 1e-5)) < 1e-4, (flag, u["tag"], "invstd", _rel(st[C:2 * C], torch.rsqrt(var + 1e-5)))
-            first_y.append(saved["blocks"][0][2]["y"].interior().clone())
+                        st = u.stats
+                        assert _rel(st[:C], mean) < 1e-4 + 1e-4 * float(mean.abs().max() == 0), (flag, u.tag, "mean")
+                        assert _rel(st[C:2 * C], torch.rsqrt(var + 1e-5)) < 1e-4, (flag, u.tag, "invstd", _rel(st[C:2 * C], torch.rsqrt(var + 1e-5)))
+            first_y.append(saved["blocks"][0][2].y.interior().clone())
         finally:
             engine.BN_STATS_IN_CONV = True
     # same input, statistics equal to rounding: the first unit's activation agrees up to single bf16 ulps (the tuner may run

@@ -1,8 +1,13 @@
 """The host side of every forward / training step launches exactly what it launched before the executors were split by layer kind: the launch
-trace (tests/launch_trace.py) of every scenario -- each one a branch of ``Plan.forward`` / ``Plan.backward`` / ``ResNetPlan`` -- equals the one
-recorded in launch_trace_cpu.json, which was written from a checkout of the commit before that refactor:
+trace (tests/launch_trace.py) of every scenario -- each one a branch of ``Plan.forward`` / ``Plan.backward`` / ``ResNetPlan`` / ``BNPlan`` -- equals the
+one recorded in launch_trace_cpu.json, which was written from a checkout of the commit before that refactor:
 
     python tests/launch_trace.py --root <checkout of the parent commit> --write tests/launch_trace_cpu.json
+
+The ``bn_train_*`` scenarios, ``resnet_forward_twice`` and the ``resnet_*_no_BN_STATS_IN_CONV`` / ``resnet_train_no_WGRAD_STREAM`` scenarios were added
+to the file in the same way from commit cff3529 ("Add BatchNorm variant of YOLOv1"), the parent of the refactor that gave the two conv -> BatchNorm
+executors one unit record, packer, walk and backward helper (yolo/conv_bn.py); that recording left every older entry as it was.  A trace depends on
+the launch plans that earlier scenarios of the same process entered into the process-wide table, so the file is recorded, and compared, over whole runs.
 
 A kernel change that moves launches on purpose regenerates the file from its own tree and says so."""
 

@@ -1,4 +1,4 @@
-"""autograd bridges: a whole plan (or the whole trainable ResNet trunk) is ONE autograd node -- no per-layer graph."""
+"""autograd bridges: a whole plan (or the whole trainable ResNet trunk, or BatchNorm chain) is ONE autograd node -- no per-layer graph."""
 
 from __future__ import annotations
 
@@ -28,8 +28,9 @@ class PlanFunction(torch.autograd.Function):
         return (None, None, None, gx, *pg)
 
 
-class ResNetTrainFunction(torch.autograd.Function):
-    """autograd bridge of the trainable ResNet trunk: one node for the whole trunk (ResNetPlan.forward_train / backward_train)."""
+class ConvBNTrainFunction(torch.autograd.Function):
+    """autograd bridge of the conv -> BatchNorm executors: one node for the whole trainable ResNet trunk or BatchNorm chain
+    (``plan.forward_train`` / ``plan.backward_train`` of a ResNetPlan or a BNPlan)."""
 
     @staticmethod
     def forward(ctx, plan, frozen: bool, x: torch.Tensor, *params):
@@ -41,10 +42,15 @@ class ResNetTrainFunction(torch.autograd.Function):
     @_hip.device_guard
     def backward(ctx, gout):
         if ctx.saved is None:
-            raise RuntimeError("backward through a ResNet trunk forward that was already consumed")
+            raise RuntimeError(f"backward through {ctx.plan.WHAT} forward that was already consumed")
+        if ctx.needs_input_grad[2] and ctx.plan.NO_INPUT_GRAD is not None:
+            raise NotImplementedError(ctx.plan.NO_INPUT_GRAD)
         grads = ctx.plan.backward_train(ctx.saved, gout)
         ctx.saved = None
         return (None, None, None) + tuple(grads.get(p) if p.requires_grad else None for p in ctx.params)
+
+
+ResNetTrainFunction = BNTrainFunction = ConvBNTrainFunction          # the names the two executors were given their bridges under
 
 
 def run_plan(plan: Plan, x, drop_training: bool) -> torch.Tensor:

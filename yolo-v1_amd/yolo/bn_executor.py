@@ -13,14 +13,13 @@ import torch.nn as nn
 
 from . import _hip
 from ._hip import EPI_NONE, PoolDesc, check, ptr
+from .autograd import BNTrainFunction
 from .config import CONFIG as CFG
+from .conv_bn import Unit, _ConvBNBase, _TrainBackward
 from .plans import igemm_call
-from .resnet_executor import _ConvBNBase, _TrainBackward
-from .runtime import RT, Act, _igemm, _timed
+from .runtime import RT, _igemm, _timed, f32, is_stem, require_pool2
 
 SLOPE = 0.1
-ONE_IN_FLIGHT = ("BNPlan: a later training forward has reused this forward's activation buffers -- call backward() "
-                 "before the next forward of the same backbone (one forward in flight per plan)")
 NO_INPUT_GRAD = "the BatchNorm chain (BNPlan) computes no gradient with respect to its input image: detach the input"
 BN_LRELU_NOT_DETERMINISTIC = ("EngineConfig.DETERMINISTIC does not cover a BatchNorm backbone in training mode: its batch statistics and the sums of its "
                               "backward pass are fp64 atomics (bn.hip).  Train without --deterministic, or without --batch-norm")
@@ -35,12 +34,12 @@ class BNPlan(_ConvBNBase):
     The statistics always come from the separate pass (stats_ready = 0): ``BN_STATS_IN_CONV`` is the ResNet trunk's switch and is not read here.
     frozen: eval() mode with gradients -- running statistics, nothing updated, no batch terms in the backward pass."""
 
+    WHAT = "a BatchNorm chain"
+    NO_INPUT_GRAD = NO_INPUT_GRAD
+
     def __init__(self, units: list):
+        super().__init__()
         self.units = units           # [(conv, bn, pool, first)]
-        self._bn_scratch = None
-        self._bufs: dict = {}
-        self._train_gen = 0
-        self.trace = None            # tests: a list that backward_train fills with (unit index, "gout" | "gx", NCHW fp32 gradient)
 
     @staticmethod
     def from_modules(mods) -> "BNPlan":
@@ -56,7 +55,7 @@ class BNPlan(_ConvBNBase):
                 raise ValueError("BNPlan: only LeakyReLU(0.1)")
             if bn.num_features != conv.out_channels or bn.weight is None or not bn.track_running_stats or bn.num_features > 2048:
                 raise ValueError(f"BNPlan: {bn} must be affine with running statistics, at most 2048 channels, behind a conv of as many output channels")
-            first = conv.in_channels == 3 and k == 7 and s == 2 and p == 3
+            first = is_stem(conv)
             if first and (i != 0 or conv.out_channels != 64):
                 raise ValueError("BNPlan: the 7x7/s2 stem has 64 output channels and comes first")
             if not first and (not ((k == 3 and p == 1) or (k == 1 and p == 0)) or s not in (1, 2) or conv.in_channels % 64 or conv.out_channels % 64):
@@ -64,11 +63,7 @@ class BNPlan(_ConvBNBase):
             i += 3
             pool = i < len(mods) and isinstance(mods[i], nn.MaxPool2d)
             if pool:
-                m = mods[i]
-                ks = m.kernel_size if isinstance(m.kernel_size, int) else m.kernel_size[0]
-                st = m.stride if isinstance(m.stride, int) else m.stride[0]
-                if ks != 2 or st != 2:
-                    raise ValueError("BNPlan: only MaxPool2d(2,2)")
+                require_pool2(mods[i], "BNPlan: ")
                 i += 1
             units.append((conv, bn, pool, first))
         if not units:
@@ -86,40 +81,34 @@ class BNPlan(_ConvBNBase):
         """Returns (out, saved).  One forward may be in flight per plan (the buffers are reused step to step)."""
         _hip.require_cuda(x)
         L_, st = RT.lib(), RT.stream()
-        pk = self._pack_train_units([(i, conv, bn, first) for i, (conv, bn, _, first) in enumerate(self.units)])
+        packable = [(i, conv, bn, first) for i, (conv, bn, _, first) in enumerate(self.units)]
+        self._train_pk = self._pack(packable, self._train_pk, dgrad=True)
+        pk = self._train_pk[1]
         N, dev = x.shape[0], x.device
         acc, ss = self._scratch(dev)
-        nstat = 4 * sum(bn.num_features for (_, bn, _, _) in self.units)
-        if getattr(self, "_stats", None) is None or self._stats.numel() < nstat or self._stats.device != dev:
-            self._stats = torch.empty(nstat, dtype=torch.float32, device=dev)
+        stat = self._stat_arena(packable, dev)
         if self.units[0][3]:
-            cur, Ho, Wo = self._stem_input(x, st)
+            cur = self._stem_input(x, st)
         else:
-            xd = x.detach()
-            if xd.dtype != torch.float32 or not xd.is_contiguous():
-                xd = xd.float().contiguous()
             C0 = self.units[0][0].in_channels
             if x.shape[1] != C0:
                 raise RuntimeError(f"BNPlan: the input has {x.shape[1]} channels, the first conv expects {C0}")
             cur = self._act("in", N, x.shape[2], x.shape[3], C0, 1, dev)
-            check(L_.yolo_nchw_f32_to_nhwc_bf16(ptr(xd), N, C0, x.shape[2], x.shape[3], cur.p, C0, 1, 1, st), "nchw->nhwc")
-        recs, cursor = [], 0
+            check(L_.yolo_nchw_f32_to_nhwc_bf16(ptr(f32(x)), N, C0, x.shape[2], x.shape[3], cur.p, C0, 1, 1, st), "nchw->nhwc")
+        recs = []
         for i, (conv, bn, pool, first) in enumerate(self.units):
             wf, wd, _, _ = pk[i]
             C = conv.out_channels
+            k, s, p, Ho, Wo = self._geom(cur, conv)
+            z = self._act((i, "z"), N, Ho, Wo, C, 1, dev)
             if first:
-                k, s, p = 7, 2, 3
-                z = self._act((i, "z"), N, Ho, Wo, C, 1, dev)
                 with _timed(str(i), "igemm", 2.0 * N * Ho * Wo * 64 * 147):
                     _igemm(L_, self._stem_desc(cur, z, EPI_NONE, 1.0), cur.p, ptr(wf), None, None, z.p, st, "igemm stem")
             else:
-                k, s, p, Ho, Wo = self._geom(cur, conv)
-                z = self._act((i, "z"), N, Ho, Wo, C, 1, dev)
                 d = self._desc(cur, p, s, k, z, EPI_NONE, 1.0)
                 with _timed(str(i), "igemm", 2.0 * N * Ho * Wo * C * conv.in_channels * k * k):
                     igemm_call(d, cur.p, ptr(wf), None, None, z.p, st, f"igemm {i}")
-            stats = self._stats[cursor: cursor + 4 * C]
-            cursor += 4 * C
+            stats = stat(C)
             fused = pool and CFG.BN_POOL_FUSED and Ho % 2 == 0 and Wo % 2 == 0
             y = self._act((i, "y"), N, Ho // 2 if fused else Ho, Wo // 2 if fused else Wo, C, 1, dev)
             mom = 0.1 if bn.momentum is None else bn.momentum
@@ -133,10 +122,8 @@ class BNPlan(_ConvBNBase):
                 out = self._act((i, "yp"), N, Ho // 2, Wo // 2, C, 1, dev)
                 pd = PoolDesc(N, Ho, Wo, C, y.halo, out.halo)
                 check(L_.yolo_maxpool2_fwd(ctypes.byref(pd), y.p, out.p, st), f"maxpool2_fwd {i}")
-            recs.append({"tag": i, "conv": conv, "bn": bn, "x": cur, "z": z, "y": y, "out": out, "pool": pool, "fused": fused, "first": first, "stats": stats,
-                         "wd": wd, "k": k, "s": s, "p": p})
+            recs.append(Unit(i, conv, bn, cur, z, y, stats, wd, k, s, p, first, pool=pool, fused=fused, out=out))
             cur = out
-            Ho, Wo = cur.H, cur.W
         res = self._to_nchw(cur, dev, st)
         self._train_gen += 1
         return res, {"N": N, "dev": dev, "units": recs, "out": cur, "gen": self._train_gen, "frozen": frozen}
@@ -145,76 +132,34 @@ class BNPlan(_ConvBNBase):
     def backward_train(self, saved, gout: torch.Tensor) -> dict:
         """gradients of every parameter of the chain for the forward recorded in `saved`: {parameter: fp32 gradient}."""
         L_, st = RT.lib(), RT.stream()
-        N, dev = saved["N"], saved["dev"]
-        if saved["gen"] != self._train_gen:
-            raise RuntimeError(ONE_IN_FLIGHT)
-        acc, _ = self._bn_scratch
-        self._bwd_scratch(dev)
         recs = saved["units"]
-        B = _TrainBackward(self, [u["conv"] for u in recs if not u["first"]], N, dev, st)
-        out = saved["out"]
-        gout = gout.detach()
-        if gout.dtype != torch.float32 or not gout.is_contiguous():
-            gout = gout.float().contiguous()
-        g = self._act(("g", "out"), N, out.H, out.W, out.C, 1, dev)
-        check(L_.yolo_nchw_f32_to_nhwc_bf16(ptr(gout), N, out.C, out.H, out.W, g.p, out.C, 1, 1, st), "gout nchw->nhwc")
+        B = _TrainBackward(self, saved, [u.conv for u in recs if not u.first], st)
+        N, dev = B.N, B.dev
+        g = B.seed(saved["out"], gout)
         for u in reversed(recs):
-            i, z, y, bn, s = u["tag"], u["z"], u["y"], u["bn"], u["s"]
+            i, z, y, bn = u.tag, u.z, u.y, u.bn
             C = z.C
-            if self.trace is not None:
-                self.trace.append((i, "gout", g.interior().float().permute(0, 3, 1, 2).contiguous()))
-            if u["pool"] and not u["fused"]:
+            B.note(i, "gout", g)
+            if u.pool and not u.fused:
                 gy = self._act((i, "gy"), N, z.H, z.W, C, 1, dev)          # an odd last row / column is never written: it stays zero
                 pd = PoolDesc(N, z.H, z.W, C, y.halo, g.halo)
                 check(L_.yolo_maxpool2_bwd_lrelu(ctypes.byref(pd), y.p, g.p, 1.0, gy.p, st), f"maxpool2_bwd {i}")
                 g = gy
-            if u["first"] or s == 1:
-                dz = self._act((i, "dz"), N, z.H, z.W, C, 1, dev)
-                strides = (dz.img_stride, dz.row_stride, dz.px_stride, dz.interior_off())
-            else:           # zero-stuffed on the conv's input grid: the form yolo_wgrad and the data gradient read
-                xin = u["x"]
-                dz = self._act((i, "dz"), N, xin.H, xin.W, C, 1, dev)
-                strides = (dz.img_stride, s * dz.row_stride, s * dz.px_stride, dz.interior_off())
-            dg, db = torch.empty_like(bn.weight, dtype=torch.float32), torch.empty_like(bn.bias, dtype=torch.float32)
-            check(L_.yolo_batchnorm_bwd_lrelu(g.p, g.halo, z.p, z.halo, N, z.H, z.W, C, ptr(bn.weight.detach()), ptr(u["stats"]), SLOPE,
-                                                   1 if u["fused"] else 0, dz.p, strides[0], strides[1], strides[2], strides[3],
-                                                   1 if saved["frozen"] else 0, ptr(dg), ptr(db), ptr(acc), ptr(self._coef), st), f"batchnorm_bwd_lrelu {i}")
-            B.grads[bn.weight], B.grads[bn.bias] = dg, db
-            if u["first"]:
+            dz, strides, dg, db = B.bn_outputs(u)
+            check(L_.yolo_batchnorm_bwd_lrelu(g.p, g.halo, z.p, z.halo, N, z.H, z.W, C, ptr(bn.weight.detach()), ptr(u.stats), SLOPE, 1 if u.fused else 0,
+                                                   dz.p, *strides, 1 if saved["frozen"] else 0, ptr(dg), ptr(db), ptr(B.acc), ptr(self._coef), st),
+                  f"batchnorm_bwd_lrelu {i}")
+            if u.first:
                 B.flush()
-                B.grads[u["conv"].weight] = self._stem_wgrad(u["x"], dz, u["conv"], N, z.H, z.W, dev, st)
+                B.stem_wgrad(u, dz)
                 break
             B.wgrad(u, dz)
             if i > 0:
                 g = B.dgrad(u, dz, None)
-                if self.trace is not None:
-                    self.trace.append((i, "gx", g.interior().float().permute(0, 3, 1, 2).contiguous()))
-            if len(B.pending) >= 24:
-                B.flush()
+                B.note(i, "gx", g)
+            B.flush(24)
         B.flush()
-        B.finish()
-        return B.grads
-
-
-class BNTrainFunction(torch.autograd.Function):
-    """autograd bridge of a BatchNorm chain: one node for the whole chain (BNPlan.forward_train / backward_train)."""
-
-    @staticmethod
-    def forward(ctx, plan: BNPlan, frozen: bool, x: torch.Tensor, *params):
-        out, saved = plan.forward_train(x, frozen)
-        ctx.plan, ctx.saved, ctx.params = plan, saved, params
-        return out
-
-    @staticmethod
-    @_hip.device_guard
-    def backward(ctx, gout):
-        if ctx.saved is None:
-            raise RuntimeError("backward through a BatchNorm chain forward that was already consumed")
-        if ctx.needs_input_grad[2]:
-            raise NotImplementedError(NO_INPUT_GRAD)
-        grads = ctx.plan.backward_train(ctx.saved, gout)
-        ctx.saved = None
-        return (None, None, None) + tuple(grads.get(p) if p.requires_grad else None for p in ctx.params)
+        return B.finish()
 
 
 def run_bn_plan(plan: BNPlan, x, training: bool) -> torch.Tensor:

@@ -1,12 +1,13 @@
-"""Facade of the engine (round 3: the 2,000-line engine.py of round 2 is now five modules).
+"""Facade of the engine (round 3: the 2,000-line engine.py of round 2 is now a handful of modules).
 
     config.py           EngineConfig -- every switch and measurement hook as ONE object (process-wide ``CONFIG``, per plan ``plan.cfg``)
     runtime.py          workspaces + streams: Act, scratch pools, side streams, per-launch timers, the patchable hooks ``RT``
     plans.py            launch plans of yolo_igemm: shipped table, deterministic default, tuner, ``igemm_call``
     executor.py         Layer / Plan: the YOLOv1 conv / pool / FC executor (forward, backward on two streams)
+    conv_bn.py          what the two conv -> BatchNorm executors share: plan buffers, the per-pass unit record, weight packer, stem, backward steps
     resnet_executor.py  ResNetPlan: ResNet-50 trunk (inference, frozen-training, trainable forward / backward)
     bn_executor.py      BNPlan: conv -> BatchNorm -> LeakyReLU [-> pool] chains of the BatchNorm YOLOv1 variant (training forward / backward)
-    autograd.py         PlanFunction, ResNetTrainFunction, run_plan
+    autograd.py         PlanFunction, ConvBNTrainFunction (= ResNetTrainFunction = BNTrainFunction), run_plan
 
 This module re-exports their names, and reads / writes of a switch (``engine.FUSE_POOL = False``, ``engine.TIMERS = []``) or of a runtime hook
 (``engine.lib = fake``) go to ``config.CONFIG`` / ``runtime.RT``, so code written against round 2's module-level globals keeps working."""
@@ -23,8 +24,8 @@ from . import executor as _executor
 from . import plans as _plans
 from . import resnet_executor as _resnet_executor
 from . import runtime as _runtime
-from .autograd import PlanFunction, ResNetTrainFunction, run_plan  # noqa: F401
-from .bn_executor import BNPlan, BNTrainFunction, run_bn_plan  # noqa: F401
+from .autograd import BNTrainFunction, ConvBNTrainFunction, PlanFunction, ResNetTrainFunction, run_plan  # noqa: F401
+from .bn_executor import BNPlan, run_bn_plan  # noqa: F401
 from .config import CONFIG, EngineConfig  # noqa: F401
 from .executor import Layer, Plan  # noqa: F401
 from .plans import (PLAN_FILE, _TILE, _TILE_COST, _TUNED, _default_plan, _key_str, _persist_ok, _pipe_ok, _pipe_pool_ok, _run_plan_igemm,  # noqa: F401

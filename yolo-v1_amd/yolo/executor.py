@@ -28,8 +28,8 @@ from . import _hip
 from ._hip import (EPI_BIAS, EPI_BIAS_LRELU, EPI_MUL_DLRELU, EPI_NONE, ConvPackItem, ConvUnpackItem, IgemmDesc, PoolDesc, WgradDesc, check, ptr)
 from .config import CONFIG as CFG
 from .plans import igemm_call
-from .runtime import (RT, Act, _attach_wgrad_slabs, _EventSlot, _igemm, _on_side_stream, _round_up, _timed, desc_aux, igemm_desc, rows_desc,
-                      stem_tiles_ok)
+from .runtime import (RT, Act, _attach_wgrad_slabs, _EventSlot, _igemm, _on_side_stream, _round_up, _timed, desc_aux, f32, igemm_desc, is_stem,
+                      require_pool2, rows_desc, side_stream, stem_tiles_ok)
 
 
 @dataclass
@@ -115,15 +115,6 @@ class Plan:
                             for li in order}
         return self.arena
 
-    @staticmethod
-    def _side_stream(dev) -> "torch.cuda.Stream":
-        """the second stream of the backward pass (weight gradients): one per device, shared by all plans (kept outside the plan
-        objects, which are deep-copied with their modules)"""
-        key = torch.device(dev).index
-        if key not in RT._SIDE_STREAMS:
-            RT._SIDE_STREAMS[key] = RT.STREAMS.side(dev, CFG.SIDE_LOW)
-        return RT._SIDE_STREAMS[key]
-
     def _layer_done(self, li: int):
         if self.arena is not None and self.on_grad_ready is not None:
             _, _, a, b = self.arena_views[li]
@@ -146,7 +137,7 @@ class Plan:
                 act = isinstance(nxt, nn.LeakyReLU)
                 if act and abs(nxt.negative_slope - Plan.SLOPE) > 1e-12:
                     raise ValueError("only LeakyReLU(0.1) is fused")
-                first = (m.in_channels == 3 and k == 7 and s == 2 and p == 3)
+                first = is_stem(m)
                 if not first and not ((k == 3 and p == 1) or (k == 1 and p == 0)) or (not first and s not in (1, 2)):
                     raise ValueError(f"unsupported conv geometry {m}")
                 if not first and (m.in_channels % 32 or m.out_channels % 8):
@@ -155,10 +146,7 @@ class Plan:
                                     weight=m.weight, bias=m.bias, first=first))
                 i += 2 if act else 1
             elif isinstance(m, nn.MaxPool2d):
-                ks = m.kernel_size if isinstance(m.kernel_size, int) else m.kernel_size[0]
-                st = m.stride if isinstance(m.stride, int) else m.stride[0]
-                if ks != 2 or st != 2:
-                    raise ValueError("only MaxPool2d(2,2)")
+                require_pool2(m)
                 layers.append(Layer("pool"))
                 i += 1
             elif isinstance(m, nn.Flatten):
@@ -192,10 +180,7 @@ class Plan:
         return L.kind == "conv" and not L.first and L.Cout % 64 == 0 and L.Cin % 64 == 0 and L.K * L.K <= 9
 
     def _src(self, L: Layer):
-        wsrc = L.weight.detach()
-        if wsrc.dtype != torch.float32 or not wsrc.is_contiguous():
-            wsrc = wsrc.float().contiguous()
-        return wsrc
+        return f32(L.weight)
 
     def _pack_all(self, need_dgrad: bool):
         """Refresh every stale conv operand of the plan in ONE launch (yolo_pack_conv_weights_multi)."""
@@ -431,13 +416,12 @@ class Plan:
         N, dev = x.shape[0], x.device
         batch = isinstance(x, U8Batch)
         u8 = batch or u8_size is not None
-        if not batch:
-            x = x.detach()
         if not u8:
             if x.dim() != 4 or x.shape[1] != self.in_channels:
                 raise RuntimeError(f"expected input of shape (N, {self.in_channels}, H, W), got {tuple(x.shape)}")
-            if x.dtype != torch.float32 or not x.is_contiguous():
-                x = x.float().contiguous()
+            x = f32(x)
+        elif not batch:
+            x = x.detach()
         key, ws = self._workspace(N, x.shape if (batch or not u8) else (N, 3, u8_size[0], u8_size[1]), dev, train)
         self._pack_all(train)
         a = ws["in"]
@@ -674,9 +658,7 @@ class Plan:
     def backward(self, saved, gout: torch.Tensor, need_gx: bool):
         """gout: gradient of the plan output (same shape as forward's out).  Returns (gx or None, [param grads])."""
         b = _Backward(self, saved, need_gx)
-        gout = gout.detach()
-        if gout.dtype != torch.float32 or not gout.is_contiguous():
-            gout = gout.float().contiguous()
+        gout = f32(gout)
         with b.on_side():
             b.scratch.zero_()
         li = len(self.layers) - 1
@@ -1030,7 +1012,7 @@ class _Backward:
             self.scratch = self.ws["misc"]["wgrad_scratch"] = torch.empty(max(tot, 1), dtype=torch.float32, device=dev)
         self.bscratch = torch.zeros(max(btot, 1), dtype=torch.float32, device=dev)
         self.main_t = RT.STREAMS.current(dev)
-        self.side_t = plan._side_stream(dev) if plan.c.WGRAD_STREAM else None
+        self.side_t = side_stream(dev) if plan.c.WGRAD_STREAM else None
         self.det = bool(plan.c.DETERMINISTIC)     # every yolo_wgrad launch with slabs (scratch per stream), no norm hint (EngineConfig.DETERMINISTIC)
         self.grads: dict[int, tuple] = {}
         self.pending: list[tuple] = []     # conv gradients waiting for their packed -> OIHW conversion

@@ -22,6 +22,7 @@ import torch.nn as nn
 
 from . import engine
 from .config import CONFIG
+from .conv_bn import _ConvBNBase
 
 
 BN_STATS_NOT_DETERMINISTIC = ("EngineConfig.DETERMINISTIC does not cover the ResNet trunk in training mode: its BatchNorm batch statistics are summed with "
@@ -93,7 +94,7 @@ class _BNFeatures:
     with gradients, the training executor ``engine.BNPlan`` (batch statistics in train(), running statistics in eval()); without, the BatchNorm layers
     folded into plain ``[Conv2d(bias), LeakyReLU, MaxPool2d]`` modules that the ordinary ``engine.Plan`` runs -- same shapes, same launch table as the
     plain network.  The folded modules are shadows outside the module tree (no state-dict keys); they are refreshed when a parameter's or buffer's
-    ``_version`` changes, as ``ResNetPlan._pack_all`` does."""
+    ``_version`` changes, as the folded operands of ``ResNetPlan.forward`` are."""
 
     def __init__(self, features: nn.Sequential):
         self.features = features
@@ -134,7 +135,7 @@ class _BNFeatures:
         if ver != self._ver:
             with torch.no_grad():
                 for conv, bn, sh in self._pairs:
-                    w, b = engine.ResNetPlan._fold(conv, bn)
+                    w, b = _ConvBNBase._fold(conv, bn)
                     sh.weight.copy_(w)
                     sh.bias.copy_(b)
             self._ver = ver

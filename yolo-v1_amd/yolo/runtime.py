@@ -47,6 +47,25 @@ def desc_aux(d: IgemmDesc, a: "Act", mul: int = 1, py: int = 0, px: int = 0) -> 
     d.aux_off = a.interior_off() + py * a.row_stride + px * a.px_stride
 
 
+def f32(t: torch.Tensor) -> torch.Tensor:
+    """t detached, as contiguous fp32: t's own storage where it is that already"""
+    t = t.detach()
+    return t if t.dtype == torch.float32 and t.is_contiguous() else t.float().contiguous()
+
+
+def is_stem(conv) -> bool:
+    """the 7x7/s2/p3 conv over an RGB image: the layer that reads the NHWC4 input and has the dedicated stem kernels"""
+    return conv.in_channels == 3 and conv.kernel_size[0] == 7 and conv.stride[0] == 2 and conv.padding[0] == 3
+
+
+def require_pool2(m, who: str = "") -> None:
+    """the only pool the YOLOv1 executors run: MaxPool2d(2,2)"""
+    ks = m.kernel_size if isinstance(m.kernel_size, int) else m.kernel_size[0]
+    st = m.stride if isinstance(m.stride, int) else m.stride[0]
+    if ks != 2 or st != 2:
+        raise ValueError(who + "only MaxPool2d(2,2)")
+
+
 def stem_tiles_ok(Cout: int, Hout: int, Wout: int) -> bool:
     """the dedicated 7x7/s2 stem kernels (forward, weight gradient, fused pool backward) cover this output map: 64 channels in 8 x 16-pixel tiles"""
     return Cout == 64 and Hout % 8 == 0 and Wout % 16 == 0
@@ -68,6 +87,13 @@ class _Streams:
         return torch.cuda.stream(s)
 
 
+def side_stream(dev) -> "torch.cuda.Stream":
+    """the second stream of a backward pass (weight gradients): one per device, shared by all plans (kept outside the plan
+    objects, which are deep-copied with their modules)"""
+    key = torch.device(dev).index
+    if key not in RT._SIDE_STREAMS:
+        RT._SIDE_STREAMS[key] = RT.STREAMS.side(dev, CFG.SIDE_LOW)
+    return RT._SIDE_STREAMS[key]
 
 
 class _on_side_stream:
