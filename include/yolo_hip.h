@@ -517,6 +517,58 @@ int yolo_sgd_step_multi_bg(const yolo_sgd_tensor *t, int count, float lr, float 
                            int nesterov, int first_step, const double *norm_sq, float max_norm, const float *skip_flag,
                            int workgroups, yolo_stream_t stream);
 
+/* LARS (You, Gitman, Ginsburg 2017: layer-wise adaptive rate scaling) in the optimizer slot of the reference's train step
+ * (src/yolo/training/trainer.py:79-95), for the large effective batches of accumulation x ranks; the reference has no such optimizer, the
+ * entries stand beside its clip_grad_norm_ + optimizer.step().  Two passes (lars.hip).
+ *
+ * Per-tensor sums of squares, order-fixed, no atomics (the structure of yolo_sumsq_f32_multi_fixed): a workgroup owns one 65536-element
+ * slice of one tensor and stores sum p^2 and sum g^2 of it in scratch slots 2k, 2k + 1 (k = its index); one workgroup per tensor adds the
+ * tensor's slots in a fixed order and STORES norms[2i] = sum p[i]^2, norms[2i+1] = sum g[i]^2 (doubles; not accumulated, empty tensors
+ * give 0, 0); lists longer than YOLO_MT_MAX take several launches, each reusing the scratch from slot 0.  g_total (NULL: none):
+ * *g_total = norms[1] + norms[3] + .. in rising order, the global squared gradient norm for the folded clip (trainer.py:79-95), stored.
+ * Two calls on the same inputs give the same bits, so EngineConfig.DETERMINISTIC needs no second path.  scratch: scratch_slots >=
+ * yolo_lars_norm_slots doubles, 8-B aligned, not shared with a launch in flight on another stream; norms: 2 * count doubles.
+ * YOLO_E_ARG: a null pointer, count < 0, n[i] < 0, scratch too small.  YOLO_E_UNSUPPORTED: a p[i] or g[i] not 16-B aligned, norms or
+ * g_total not 8-B aligned.  Every tensor is checked before the first launch: a refused call launches nothing. */
+int yolo_lars_norm_slots(const long *n, int count, long *slots);
+int yolo_lars_norms_multi(const float *const *p, const float *const *g, const long *n, int count, double *scratch, long scratch_slots,
+                          double *norms, double *g_total, yolo_stream_t stream);
+/* The step, with the folded clip_grad_norm_, skip flag and bf16 shadow of the SGD entries (trainer.py:79-95).  Per tensor, in fp64, from
+ * the two doubles of yolo_lars_norms_multi:
+ *     wn = sqrt(norms[0]) ;  gn = (double)clip * sqrt(norms[1])          clip = min(1, max_norm / (sqrt(*norm_sq) + 1e-6)) in fp32, 1 when NULL
+ *     trust = (adapt && wn > 0 && gn > 0) ? (float)((double)eta * wn / (gn + (double)weight_decay * wn + (double)eps)) : 1
+ * Per element, in fp32, every a * b + c one fused multiply-add (all three forms: the same bits):
+ *     g = grad * clip ;  g = g + weight_decay * p (weight_decay != 0) ;  g = g * trust
+ *     buf = first_step ? g : momentum * buf + g  (momentum != 0; else buf is not touched, may be NULL, and g is used) ;  p = p - lr * buf
+ *     p_bf16 = bf16(p)
+ * -- the regularised gradient scaled by the trust ratio, then torch.optim.SGD(weight_decay=0); no dampening, no Nesterov.  adapt == 0: the
+ * plain clipped SGD step, bit for bit.  *skip_flag != 0 updates nothing.
+ * YOLO_E_ARG: a null pointer, a negative size / lr / momentum / weight_decay / eta / eps, adapt != 0 with norms == NULL, workgroups outside
+ * 1 .. 256, more than YOLO_MT_MAX tensors in the background form.  YOLO_E_UNSUPPORTED: p / g / buf not 16-B aligned, p_bf16 or norms not
+ * 8-B aligned.  Either way nothing is launched. */
+typedef struct yolo_lars_tensor {
+    float *p;            /* parameter, updated in place */
+    const float *g;      /* gradient */
+    float *buf;          /* momentum_buffer */
+    void *p_bf16;        /* optional bf16 shadow of p in the same layout (NULL: none) */
+    const double *norms; /* the 2 doubles of this tensor: sum p^2, sum g^2 (NULL when adapt == 0) */
+    long n;              /* elements */
+    int adapt;           /* 0: trust ratio 1 (biases, BatchNorm gamma / beta) */
+} yolo_lars_tensor;
+/* One tensor (trainer.py:79-95, the optimizer.step() of one parameter). */
+int yolo_lars_step(float *p, const float *g, float *buf, long n, const double *norms, int adapt, float lr, float momentum, float weight_decay,
+                   float eta, float eps, int first_step, const double *norm_sq, float max_norm, void *p_bf16, const float *skip_flag,
+                   yolo_stream_t stream);
+/* A whole parameter list (trainer.py:79-95): one launch per YOLO_MT_MAX tensors, the host table copied into the kernel arguments; empty
+ * tensors are legal.  All tensors share first_step and the hyper-parameters; adapt is per tensor. */
+int yolo_lars_step_multi(const yolo_lars_tensor *t, int count, float lr, float momentum, float weight_decay, float eta, float eps,
+                         int first_step, const double *norm_sq, float max_norm, const float *skip_flag, yolo_stream_t stream);
+/* The same update (trainer.py:79-95) as a BACKGROUND pass for a second stream, like yolo_sgd_step_multi_bg: `workgroups` (1 .. 256)
+ * persistent workgroups of 1024 threads, each holding one CU to itself.  At most YOLO_MT_MAX tensors. */
+int yolo_lars_step_multi_bg(const yolo_lars_tensor *t, int count, float lr, float momentum, float weight_decay, float eta, float eps,
+                            int first_step, const double *norm_sq, float max_norm, const float *skip_flag, int workgroups,
+                            yolo_stream_t stream);
+
 /* Exponential moving average of the weights, the copy a detector validates and ships: replaces
  * torch.optim.swa_utils.get_ema_multi_avg_fn / torch._foreach_lerp_(ema, params, 1 - decay) (the reference keeps no EMA; its
  * train step is src/yolo/training/trainer.py:79-95, and the average follows optimizer.step()).  Per element, in fp32:

@@ -58,10 +58,16 @@ def main():
     ap.add_argument("--batch-size", type=int, default=64, help="per process")
     ap.add_argument("--num-workers", type=int, default=8)
     ap.add_argument("--epochs", type=int, default=90)
-    ap.add_argument("--optimizer", choices=["adam", "sgd"], default="sgd")
+    ap.add_argument("--optimizer", choices=["adam", "sgd", "lars"], default="sgd",
+                    help="lars: layer-wise adaptive rate scaling on top of SGD with momentum, for the large effective batches of --accum-steps x ranks "
+                         "(yolo.optim.LARS; biases and BatchNorm gamma / beta are neither adapted nor decayed).  Use it with --warmup-steps")
     ap.add_argument("--lr", type=float, default=1e-2)
-    ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd only")
+    ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd / lars only")
     ap.add_argument("--nesterov", action="store_true", help="--optimizer sgd only")
+    ap.add_argument("--lars-eta", type=float, default=1e-3, help="--optimizer lars only: the trust coefficient")
+    ap.add_argument("--warmup-steps", type=int, default=0,
+                    help="linear learning-rate warm-up: optimizer step k of the run (from 0) runs at (k + 1) / N of the scheduled rate while k < N; "
+                         "--resume continues it.  Default 0: none")
     ap.add_argument("--weight-decay", type=float, default=5e-4)
     ap.add_argument("--lr-decay-epochs", default="30,60,80")
     ap.add_argument("--label-smoothing", type=float, default=0.0)
@@ -96,6 +102,10 @@ def main():
         ap.error("--label-smoothing must lie in [0, 1)")
     if a.accum_steps < 1:
         ap.error("--accum-steps must be at least 1")
+    if a.optimizer == "lars" and a.nesterov:
+        ap.error("--optimizer lars has no Nesterov momentum (--nesterov is --optimizer sgd only)")
+    if a.warmup_steps < 0:
+        ap.error("--warmup-steps must not be negative")
     if a.image_size < 32 or a.image_size % 32:
         ap.error("--image-size must be a multiple of 32 (the trunk halves the map five times)")
     if a.deterministic and a.batch_norm:
@@ -157,8 +167,10 @@ def main():
     criterion = SoftmaxCrossEntropy(label_smoothing=a.label_smoothing)
     params = [p for p in model.parameters() if p.requires_grad]
     if device == "cuda":
-        from yolo.optim import SGD, Adam     # fused clip(10) + Adam / SGD with momentum on the HIP kernels
-        if a.optimizer == "sgd":
+        from yolo.optim import LARS, SGD, Adam, lars_param_groups     # fused clip(10) + Adam / SGD with momentum / LARS on the HIP kernels
+        if a.optimizer == "lars":
+            optimizer = LARS(lars_param_groups(model, a.weight_decay), lr=a.lr, momentum=a.momentum, eta=a.lars_eta, max_grad_norm=10.0)
+        elif a.optimizer == "sgd":
             optimizer = SGD(params, lr=a.lr, momentum=a.momentum, weight_decay=a.weight_decay, nesterov=a.nesterov, max_grad_norm=10.0)
         else:
             optimizer = Adam(params, lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=10.0)
@@ -166,6 +178,9 @@ def main():
         # --accum-steps: this Linear layer is 1024 x classes, there is nothing worth hiding beside the next forward (train.py keeps the
         # detector's 822 MB update in the foreground under accumulation for the measured reason given there)
         optimizer.attach_plan(model.head_plan())
+    elif a.optimizer == "lars":                        # torch has none: the same class, whose CPU parameters take stock torch ops
+        from yolo.optim import LARS, lars_param_groups
+        optimizer = LARS(lars_param_groups(model, a.weight_decay), lr=a.lr, momentum=a.momentum, eta=a.lars_eta, max_grad_norm=10.0)
     elif a.optimizer == "sgd":
         optimizer = torch.optim.SGD(params, lr=a.lr, momentum=a.momentum, weight_decay=a.weight_decay, nesterov=a.nesterov)
     else:
@@ -208,6 +223,8 @@ def main():
         record["init"] = a.init
     if a.batch_norm:               # (likewise)
         record["batch_norm"] = True
+    if a.warmup_steps:             # (0: the call is that of a run without the option)
+        extra["warmup_steps"] = a.warmup_steps
     res = loop.train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, a.epochs, ckdir, save_frequency=a.save_frequency,
                      start_epoch=start_epoch, best_top1_init=best_top1, seed=a.seed, record=record, ema=ema, **extra)
     if rank == 0:

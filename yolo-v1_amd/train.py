@@ -51,9 +51,16 @@ def main():
     ap.add_argument("--epochs", type=int, default=135)
     ap.add_argument("--lr", type=float, default=1e-4)
     ap.add_argument("--weight-decay", type=float, default=5e-4)
-    ap.add_argument("--optimizer", choices=["adam", "sgd"], default="adam", help="sgd: the YOLOv1 paper's recipe (SGD with momentum)")
-    ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd only")
+    ap.add_argument("--optimizer", choices=["adam", "sgd", "lars"], default="adam",
+                    help="sgd: the YOLOv1 paper's recipe (SGD with momentum); lars: layer-wise adaptive rate scaling on top of it, for the large "
+                         "effective batches of --accum-steps x ranks (yolo.optim.LARS; biases and BatchNorm gamma / beta are neither adapted nor "
+                         "decayed).  Use it with --warmup-steps")
+    ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd / lars only")
     ap.add_argument("--nesterov", action="store_true", help="--optimizer sgd only")
+    ap.add_argument("--lars-eta", type=float, default=1e-3, help="--optimizer lars only: the trust coefficient")
+    ap.add_argument("--warmup-steps", type=int, default=0,
+                    help="linear learning-rate warm-up: optimizer step k of the run (from 0) runs at (k + 1) / N of the scheduled rate while k < N; "
+                         "--resume continues it.  Default 0: none")
     ap.add_argument("--lr-decay-epochs", default="75,105")
     ap.add_argument("--lambda-coord", type=float, default=5.0)
     ap.add_argument("--lambda-noobj", type=float, default=0.5)
@@ -103,6 +110,10 @@ def main():
         ap.error("--deterministic --batch-norm: " + BN_LRELU_NOT_DETERMINISTIC)
     if a.accum_steps < 1:
         ap.error("--accum-steps must be at least 1")
+    if a.optimizer == "lars" and a.nesterov:
+        ap.error("--optimizer lars has no Nesterov momentum (--nesterov is --optimizer sgd only)")
+    if a.warmup_steps < 0:
+        ap.error("--warmup-steps must not be negative")
     if a.augment != "reference" and a.synthetic:
         ap.error("--augment needs the VOC datasets (synthetic samples are not augmented)")
     if a.backbone_weights and a.backbone != "yolov1":
@@ -172,8 +183,10 @@ def main():
     criterion = YOLOLoss(S=7, B=2, C=20, lambda_coord=a.lambda_coord, lambda_noobj=a.lambda_noobj)
     params = [p for p in model.parameters() if p.requires_grad]
     if device == "cuda":
-        from yolo.optim import SGD, Adam     # fused clip(10) + Adam / SGD with momentum on the HIP kernels
-        if a.optimizer == "sgd":
+        from yolo.optim import LARS, SGD, Adam, lars_param_groups     # fused clip(10) + Adam / SGD with momentum / LARS on the HIP kernels
+        if a.optimizer == "lars":
+            optimizer = LARS(lars_param_groups(model, a.weight_decay), lr=a.lr, momentum=a.momentum, eta=a.lars_eta, max_grad_norm=10.0)
+        elif a.optimizer == "sgd":
             optimizer = SGD(params, lr=a.lr, momentum=a.momentum, weight_decay=a.weight_decay, nesterov=a.nesterov, max_grad_norm=10.0)
         else:
             optimizer = Adam(params, lr=a.lr, weight_decay=a.weight_decay, max_grad_norm=10.0)
@@ -187,6 +200,9 @@ def main():
             optimizer.attach_plan(model.head.hip_plan())
         elif a.batch_norm:                             # the default head behind the BatchNorm chain: a plan of its own
             optimizer.attach_plan(model.head_plan())
+    elif a.optimizer == "lars":                        # torch has none: the same class, whose CPU parameters take stock torch ops
+        from yolo.optim import LARS, lars_param_groups
+        optimizer = LARS(lars_param_groups(model, a.weight_decay), lr=a.lr, momentum=a.momentum, eta=a.lars_eta, max_grad_norm=10.0)
     elif a.optimizer == "sgd":
         optimizer = torch.optim.SGD(params, lr=a.lr, momentum=a.momentum, weight_decay=a.weight_decay, nesterov=a.nesterov)
     else:
@@ -227,6 +243,8 @@ def main():
         record = {**(record or {}), "init": a.init}
     if a.batch_norm:                      # (likewise)
         record = {**(record or {}), "batch_norm": True}
+    if a.warmup_steps:                    # (0: the call is that of a run without the option)
+        extra["warmup_steps"] = a.warmup_steps
     res = training.train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, a.epochs, ckdir,
                          save_frequency=a.save_frequency, compute_map=a.compute_map, start_epoch=start_epoch,
                          best_val_loss_init=best_val, best_map_init=best_map, seed=a.seed, record=record, ema=ema, **extra)

@@ -86,6 +86,13 @@ class SgdTensor(ctypes.Structure):
     _fields_ = [("p", c_void_p), ("g", c_void_p), ("buf", c_void_p), ("p_bf16", c_void_p), ("n", ctypes.c_long)]
 
 
+class LarsTensor(ctypes.Structure):
+    """struct yolo_lars_tensor (include/yolo_hip.h)."""
+
+    _fields_ = [("p", c_void_p), ("g", c_void_p), ("buf", c_void_p), ("p_bf16", c_void_p), ("norms", c_void_p), ("n", ctypes.c_long),
+                ("adapt", ctypes.c_int)]
+
+
 class EmaTensor(ctypes.Structure):
     """struct yolo_ema_tensor (include/yolo_hip.h)."""
 
@@ -200,6 +207,13 @@ _SIGS = {
     "yolo_sgd_step": [c_void_p, c_void_p, c_void_p, c_long, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p],
     "yolo_sgd_step_multi": [ctypes.POINTER(SgdTensor), c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_float, c_void_p, c_void_p],
     "yolo_sgd_step_multi_bg": [ctypes.POINTER(SgdTensor), c_int, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p],
+    "yolo_lars_norm_slots": [ctypes.POINTER(c_long), c_int, ctypes.POINTER(c_long)],
+    "yolo_lars_norms_multi": [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_long, c_void_p, c_void_p, c_void_p],
+    "yolo_lars_step": [c_void_p, c_void_p, c_void_p, c_long, c_void_p, c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_float, c_void_p,
+                       c_void_p, c_void_p],
+    "yolo_lars_step_multi": [ctypes.POINTER(LarsTensor), c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_float, c_void_p, c_void_p],
+    "yolo_lars_step_multi_bg": [ctypes.POINTER(LarsTensor), c_int, c_float, c_float, c_float, c_float, c_float, c_int, c_void_p, c_float, c_void_p, c_int,
+                                c_void_p],
     "yolo_ema_update": [c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p],
     "yolo_ema_update_multi": [ctypes.POINTER(EmaTensor), c_int, c_float, c_void_p, c_void_p],
     "yolo_ema_update_multi_bg": [ctypes.POINTER(EmaTensor), c_int, c_float, c_void_p, c_int, c_void_p],

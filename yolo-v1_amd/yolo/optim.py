@@ -9,6 +9,9 @@ reduced on the device and read by the update kernel, no host sync.
 
 ``SGD`` is ``torch.optim.SGD`` (the YOLOv1 paper's recipe: momentum 0.9, weight decay 5e-4) in the same slot, with the same
 ``max_grad_norm``, ``skip_if``, ``attach_plan`` and second-stream pass; what the two share lives in ``_Fused``.
+
+``LARS`` (lars.hip) scales every tensor's regularised gradient by its trust ratio and hands it to SGD with momentum, for large effective
+batches; its one norms pass per step also yields the clip norm.  ``lars_param_groups`` builds its two param groups.
 """
 
 from __future__ import annotations
@@ -183,8 +186,13 @@ class _Fused(torch.optim.Optimizer):
             plan.grad_norm_sq.clear()
         return known
 
+    def _clip_norm_sq(self, all_params):
+        """device double with the global squared gradient norm the step launches clip by (None: no clipping), enqueued on the current stream in
+        front of the first step launch"""
+        return grad_norm_sq(all_params, self._known_norms()) if self.max_grad_norm is not None else None
+
     def _step_on_device(self, all_params, loss):
-        norm = grad_norm_sq(all_params, self._known_norms()) if self.max_grad_norm is not None else None
+        norm = self._clip_norm_sq(all_params)
         skip, self.skip_if = self.skip_if, None
         self.last_skip = skip
         if skip is not None:
@@ -425,6 +433,148 @@ class SGD(_Fused):
             check(lib().yolo_sgd_step_multi_bg(tab, count, *h, BG_CUS, ctypes.c_void_p(side.cuda_stream)), "yolo_sgd_step_multi_bg")
         else:
             check(lib().yolo_sgd_step_multi(tab, count, *h, stream()), "yolo_sgd_step_multi")
+
+
+_LARS_NORMS: dict = {}
+
+
+def _lars_norms(dev, st, count: int) -> torch.Tensor:
+    """the 2 x count doubles yolo_lars_norms_multi stores, one buffer per device and stream like the scratch beside it, grown on demand"""
+    key = (dev.index, st.value or 0)
+    buf = _LARS_NORMS.get(key)
+    if buf is None or buf.numel() < 2 * count:
+        if buf is not None:
+            buf.record_stream(torch.cuda.current_stream(dev))
+        buf = _LARS_NORMS[key] = torch.empty(max(2 * count, 2), dtype=torch.float64, device=dev)
+    return buf
+
+
+class LARS(_Fused):
+    """Layer-wise adaptive rate scaling (You, Gitman, Ginsburg 2017) on yolo_lars_step_multi, for the large effective batches of
+    ``--accum-steps`` x ranks: the regularised gradient of every tensor is scaled by its trust ratio
+
+        trust = eta * |p| / (clip * |g| + weight_decay * |p| + eps)          (1 when |p| or |g| is 0, or the group carries ``adapt=False``)
+
+    and handed to SGD with momentum (no dampening, no Nesterov; the form of the common PyTorch LARS wrappers around ``torch.optim.SGD``).
+    Per step ONE yolo_lars_norms_multi call reads every parameter and gradient once and leaves |p|^2, |g|^2 per tensor and the global
+    squared gradient norm on the device (order-fixed, no atomics: the same entries serve ``EngineConfig.DETERMINISTIC``); the step launches
+    read them there, so ``max_grad_norm``, ``skip_if``, ``attach_plan`` (bf16 shadows, the background pass of the Linear layers) and
+    ``synchronize`` are ``_Fused``'s, unchanged.  The attached plans' squared-norm hints are dropped unused.  State per parameter:
+    ``momentum_buffer``.  Use ``lars_param_groups`` to keep biases and BatchNorm gamma / beta out of the adaptation and the decay."""
+
+    def __init__(self, params, lr=1e-3, momentum=0.9, weight_decay=0.0, eta=1e-3, eps=1e-8, max_grad_norm: float | None = None):
+        if lr < 0.0:
+            raise ValueError(f"Invalid learning rate: {lr}")
+        if momentum < 0.0:
+            raise ValueError(f"Invalid momentum value: {momentum}")
+        if weight_decay < 0.0:
+            raise ValueError(f"Invalid weight_decay value: {weight_decay}")
+        if eta < 0.0:
+            raise ValueError(f"Invalid eta value: {eta}")
+        if eps < 0.0:
+            raise ValueError(f"Invalid eps value: {eps}")
+        super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, eta=eta, eps=eps, adapt=True), max_grad_norm)
+        self._norms = None                        # this step's norms buffer
+        self._norm_index: dict[int, int] = {}     # id(param) -> its tensor index in it
+
+    def _step_on_cpu(self, all_params):
+        """CPU parameters: the same step in stock torch ops -- per-tensor sums of squares in double, the clip coefficient formed in fp32 as the
+        kernels form it, the trust ratio in double narrowed to fp32, then SGD.  With ``adapt=False`` it is yolo.optim.SGD's CPU step."""
+        self._known_norms()
+        sums = {id(p): (p.detach().double().pow(2).sum(), p.grad.double().pow(2).sum()) for p in all_params}
+        clip = None
+        if self.max_grad_norm is not None:
+            acc = torch.zeros((), dtype=torch.float64)
+            for p in all_params:
+                acc += sums[id(p)][1]
+            clip = (torch.tensor(self.max_grad_norm, dtype=torch.float32) / (acc.sqrt().float() + torch.tensor(1e-6, dtype=torch.float32))).clamp(max=1.0)
+        skip, self.skip_if = self.skip_if, None
+        self.last_skip = skip
+        if skip is not None and float(skip) != 0.0:
+            return
+        f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+        for group in self.param_groups:
+            momentum, wd = group["momentum"], group["weight_decay"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                g = p.grad.float()
+                if clip is not None:
+                    g = g * clip
+                if wd != 0:
+                    g = g.add(p, alpha=wd)
+                if group.get("adapt", True):
+                    wn = float(sums[id(p)][0].sqrt())
+                    gn = (float(clip) if clip is not None else 1.0) * float(sums[id(p)][1].sqrt())
+                    if wn > 0.0 and gn > 0.0:
+                        g = g * torch.tensor(f32(group["eta"]) * wn / (gn + f32(wd) * wn + f32(group["eps"])), dtype=torch.float32)
+                if momentum != 0:
+                    state = self.state[p]
+                    buf = state.get("momentum_buffer")
+                    if buf is None:
+                        buf = state["momentum_buffer"] = g.clone()
+                    else:
+                        buf.mul_(momentum).add_(g)
+                    g = buf
+                p.add_(g, alpha=-group["lr"])
+
+    def _clip_norm_sq(self, all_params):
+        """one norms call for all parameters with gradients, in the foreground; -> its g_total (None without max_grad_norm)"""
+        self._known_norms()                       # cleared, not used (FC1's own tensor could take its hint: a follow-up)
+        dev = all_params[0].device
+        grads = []
+        for p in all_params:
+            if p.dtype != torch.float32 or not p.is_contiguous():
+                raise RuntimeError("yolo.optim.LARS needs contiguous fp32 parameters")
+            grads.append(_f32c(p.grad))
+        _hip.require_cuda(*grads)
+        count = len(all_params)
+        if self._pending is not None:
+            torch.cuda.current_stream().wait_event(self._pending)    # the last background launch read the norms buffer this call overwrites
+        st = stream()
+        pp = (ctypes.c_void_p * count)(*[p.data_ptr() for p in all_params])
+        gp = (ctypes.c_void_p * count)(*[g.data_ptr() for g in grads])
+        gn = (ctypes.c_long * count)(*[p.numel() for p in all_params])
+        slots = ctypes.c_long(0)
+        check(lib().yolo_lars_norm_slots(gn, count, ctypes.byref(slots)), "yolo_lars_norm_slots")
+        scratch = _norm_scratch(dev, st, slots.value)
+        self._norms = _lars_norms(dev, st, count)
+        self._norm_index = {id(p): i for i, p in enumerate(all_params)}
+        total = torch.empty((), dtype=torch.float64, device=dev) if self.max_grad_norm is not None else None
+        check(lib().yolo_lars_norms_multi(pp, gp, gn, count, ptr(scratch), scratch.numel(), ptr(self._norms), ptr(total), st), "yolo_lars_norms_multi")
+        return total
+
+    def _entry(self, group, p, g, shadow):
+        buf, first = None, False
+        if group["momentum"] != 0:
+            state = self.state[p]
+            buf = state.get("momentum_buffer")
+            first = buf is None
+            if first:
+                buf = state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            elif not (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()):
+                raise RuntimeError("yolo.optim.LARS needs contiguous fp32 momentum buffers on the device")
+        adapt = bool(group.get("adapt", True))
+        norms = self._norms.data_ptr() + 16 * self._norm_index[id(p)] if adapt else None
+        return first, _hip.LarsTensor(p.data_ptr(), g.data_ptr(), buf.data_ptr() if buf is not None else None,
+                                      shadow.data_ptr() if shadow is not None else None, norms, p.numel(), int(adapt))
+
+    def _launch(self, group, first, tab, count, norm, skip, side):
+        h = (float(group["lr"]), float(group["momentum"]), float(group["weight_decay"]), float(group["eta"]), float(group["eps"]), int(first),
+             ptr(norm), float(self.max_grad_norm or 0.0), ptr(skip))
+        if side is not None:
+            self._norms.record_stream(side)
+            check(lib().yolo_lars_step_multi_bg(tab, count, *h, BG_CUS, ctypes.c_void_p(side.cuda_stream)), "yolo_lars_step_multi_bg")
+        else:
+            check(lib().yolo_lars_step_multi(tab, count, *h, stream()), "yolo_lars_step_multi")
+
+
+def lars_param_groups(model, weight_decay: float) -> list:
+    """the two param groups of a LARS run: tensors with ``ndim > 1`` (convolution and Linear weights: adapted, decayed) and tensors with
+    ``ndim <= 1`` (biases, BatchNorm gamma / beta: ``adapt=False``, ``weight_decay=0`` -- the plain clipped SGD step)"""
+    params = [p for p in model.parameters() if p.requires_grad]
+    return [{"params": [p for p in params if p.ndim > 1], "weight_decay": weight_decay},
+            {"params": [p for p in params if p.ndim <= 1], "weight_decay": 0.0, "adapt": False}]
 
 
 def _state_tensors(module):

@@ -20,7 +20,7 @@ import torch.distributed as dist
 
 from ..parallel import make_grad_reducer
 from .checkpoints import save_best_model, save_checkpoint
-from .trainer import _CLIP, seed_epoch
+from .trainer import _CLIP, make_warmup, seed_epoch
 
 _PARTS = ("total", "top1", "top5")
 PRINT_EVERY = 10
@@ -49,7 +49,7 @@ def _progress(epoch, batch_idx, total, parts, t0) -> None:
           f"(top1: {parts['top1']:.4f}, top5: {parts['top5']:.4f}) Time: {time.time() - t0:.2f}s")
 
 
-def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, ema=None, accum_steps: int = 1) -> dict[str, float]:
+def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, ema=None, accum_steps: int = 1, warmup=None) -> dict[str, float]:
     """One pass over ``dataloader``; returns the mean loss, top-1 and top-5 accuracy of its batches.  With ``torch.distributed`` initialised the
     gradients are averaged over the ranks before the update.  ``accum_steps`` = K > 1: K batches per optimizer step, EMA update and all-reduce
     (``trainer.train_epoch``); a last group of fewer than K batches is dropped and its losses do not enter the means."""
@@ -63,7 +63,7 @@ def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, ema
             allreduce = make_grad_reducer(model, device)
             model._yolo_grad_reducer = allreduce
     if accum_steps > 1:
-        return _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, ema, int(accum_steps), allreduce, fused_clip)
+        return _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, ema, int(accum_steps), allreduce, fused_clip, warmup)
     t0 = time.time()
     for batch_idx, (images, labels) in enumerate(dataloader):
         images = images.to(device, non_blocking=True)
@@ -77,7 +77,10 @@ def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, ema
             torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=_CLIP)
         if hasattr(optimizer, "skip_if"):
             optimizer.skip_if = getattr(parts, "device_flag", None)      # a batch with a label outside [0, K) updates nothing; the error surfaces at the read
-        optimizer.step()
+        if warmup is None:
+            optimizer.step()
+        else:
+            warmup.step()
         if ema is not None:
             ema.update(model)
         means.queued.append(parts)
@@ -88,7 +91,7 @@ def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, ema
     return means.result()
 
 
-def _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, ema, K, allreduce, fused_clip) -> dict[str, float]:
+def _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, ema, K, allreduce, fused_clip, warmup=None) -> dict[str, float]:
     """train_epoch's loop with K batches per optimizer step: ``trainer._train_epoch_accum`` with this loop's loss parts.  The accumulator is kept
     on the model like the reducer it mutes; it starts every epoch at the head of a group."""
     from ..optim import GradAccumulator
@@ -112,7 +115,10 @@ def _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, e
                 torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=_CLIP)
             if hasattr(optimizer, "skip_if"):
                 optimizer.skip_if = accum.skip_if    # one flagged batch cancels the group's step (and, through last_skip, the EMA's)
-            optimizer.step()
+            if warmup is None:
+                optimizer.step()
+            else:
+                warmup.step()
             if ema is not None:
                 ema.update(model)
             means.queued += group
@@ -141,19 +147,21 @@ def validate(model, dataloader, criterion, device) -> dict[str, float]:
 
 def train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, num_epochs: int, checkpoint_dir, save_frequency: int = 5,
           start_epoch: int = 1, best_top1_init: float | None = None, seed: int | None = None, record: dict | None = None, ema=None,
-          accum_steps: int = 1) -> dict[str, float]:
+          accum_steps: int = 1, warmup_steps: int = 0) -> dict[str, float]:
     """Epoch loop: the latest checkpoint every epoch (``yolo_latest.pth``), one every ``save_frequency`` epochs, and the best validation top-1
     (``yolo_best_top1.pth``).  Checkpoints are ``checkpoints.save_checkpoint``'s, key for key; ``record`` adds ``num_classes`` / ``image_size``
     (and ``seed`` / ``deterministic``).  ``seed``, ``ema``: as in ``trainer.train`` -- the averaged copy is the one validated.
     ``accum_steps``: batches per optimizer step (``train_epoch``).  With several ranks the conduct is ``trainer.train``'s: every rank validates
-    (the replicas are identical), rank 0 alone writes the checkpoints and prints their lines, and a barrier follows."""
+    (the replicas are identical), rank 0 alone writes the checkpoints and prints their lines, and a barrier follows.  ``warmup_steps``: the
+    linear learning-rate warm-up of ``trainer.LRWarmup``, continued across a resume."""
+    warmup = make_warmup(optimizer, warmup_steps, start_epoch, train_loader, accum_steps)
     best_top1 = -1.0 if best_top1_init is None else best_top1_init
     final_train = None
     for epoch in range(start_epoch, num_epochs + 1):
         print(f"\n===== Epoch {epoch}/{num_epochs} =====")
         if seed is not None:
             seed_epoch(seed, epoch, train_loader)
-        tr = train_epoch(model, train_loader, criterion, optimizer, device, epoch, ema=ema, accum_steps=accum_steps)
+        tr = train_epoch(model, train_loader, criterion, optimizer, device, epoch, ema=ema, accum_steps=accum_steps, **({"warmup": warmup} if warmup is not None else {}))
         print("  train:", {k: round(v, 4) for k, v in tr.items()})
         va = validate(model if ema is None else ema.module, val_loader, criterion, device)
         print("  val:  ", {k: round(float(v), 4) for k, v in va.items()})

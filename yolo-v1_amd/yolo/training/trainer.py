@@ -23,7 +23,39 @@ _PARTS = ("total", "coord", "conf_obj", "conf_noobj", "class")
 _CLIP = 10.0
 
 
-def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, writer=None, scaler=None, ema=None, accum_steps: int = 1) -> dict[str, float]:
+class LRWarmup:
+    """Linear learning-rate warm-up over the first ``steps`` optimizer steps of a run, for both epoch loops (this one and ``classify``): step k
+    (from 0) runs with every group's learning rate multiplied by (k + 1) / steps while k < steps, on top of whatever the scheduler set.  The
+    scheduled rates are put back as soon as the step is enqueued, so the scheduler (MultiStepLR multiplies the rate it finds) and the
+    checkpoints never see a warmed one.  ``done``: optimizer steps the run has behind it (a resume at epoch e: e x steps per epoch)."""
+
+    def __init__(self, optimizer, steps: int, done: int = 0):
+        self.optimizer, self.steps, self.k = optimizer, int(steps), int(done)
+
+    def step(self):
+        """``optimizer.step()``, warmed while the warm-up lasts"""
+        k, self.k = self.k, self.k + 1
+        if k >= self.steps:
+            return self.optimizer.step()
+        scheduled = [g["lr"] for g in self.optimizer.param_groups]
+        for g in self.optimizer.param_groups:
+            g["lr"] = g["lr"] * (k + 1) / self.steps
+        try:
+            return self.optimizer.step()
+        finally:
+            for g, lr in zip(self.optimizer.param_groups, scheduled):
+                g["lr"] = lr
+
+
+def make_warmup(optimizer, warmup_steps: int, start_epoch: int, train_loader, accum_steps: int = 1):
+    """the ``LRWarmup`` of a run that begins at ``start_epoch`` (None when ``warmup_steps`` is 0: no learning rate is ever written)"""
+    if not warmup_steps:
+        return None
+    return LRWarmup(optimizer, warmup_steps, done=(start_epoch - 1) * (len(train_loader) // max(int(accum_steps), 1)))
+
+
+def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, writer=None, scaler=None, ema=None, accum_steps: int = 1,
+                warmup=None) -> dict[str, float]:
     """One pass over ``dataloader``; returns the mean of each loss component.  ``ema``: a ``yolo.optim.ModelEMA`` of ``model``, moved after every
     optimizer step (on a device it is enqueued like the step itself, nothing waits).
 
@@ -47,7 +79,7 @@ def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, wri
             allreduce = make_grad_reducer(model, device)
             model._yolo_grad_reducer = allreduce
     if accum_steps > 1:
-        return _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, writer, ema, int(accum_steps), allreduce, fused_clip)
+        return _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, writer, ema, int(accum_steps), allreduce, fused_clip, warmup)
     t0 = time.time()
     for batch_idx, (images, targets) in enumerate(dataloader):
         images = images.to(device, non_blocking=True)
@@ -63,7 +95,10 @@ def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, wri
             # yolo.optim.Adam: a step whose targets the loss kernel flagged as invalid updates nothing (the error itself surfaces at
             # the read of `parts` below; the reference raises inside the loss, before any update)
             optimizer.skip_if = getattr(parts, "device_flag", None)
-        optimizer.step()
+        if warmup is None:
+            optimizer.step()
+        else:
+            warmup.step()
         if ema is not None:
             ema.update(model)
         for k in _PARTS:
@@ -81,7 +116,7 @@ def train_epoch(model, dataloader, criterion, optimizer, device, epoch: int, wri
     return {k: v / max(n, 1) for k, v in sums.items()}
 
 
-def _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, writer, ema, K, allreduce, fused_clip) -> dict[str, float]:
+def _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, writer, ema, K, allreduce, fused_clip, warmup=None) -> dict[str, float]:
     """train_epoch's loop with K batches per optimizer step.  The accumulator is kept on the model like the reducer it mutes (its buffers are as
     large as the gradients); it starts every epoch at the head of a group."""
     from ..optim import GradAccumulator
@@ -106,7 +141,10 @@ def _train_epoch_accum(model, dataloader, criterion, optimizer, device, epoch, w
                 torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm=_CLIP)
             if hasattr(optimizer, "skip_if"):
                 optimizer.skip_if = accum.skip_if    # one flagged batch cancels the group's step (and, through last_skip, the EMA's)
-            optimizer.step()
+            if warmup is None:
+                optimizer.step()
+            else:
+                warmup.step()
             if ema is not None:
                 ema.update(model)
             for done in group:
@@ -166,7 +204,7 @@ def seed_epoch(seed: int, epoch: int, train_loader=None) -> None:
 def train(model, train_loader, val_loader, criterion, optimizer, scheduler, device, num_epochs: int, checkpoint_dir,
           save_frequency: int = 5, writer=None, compute_map: bool = False, map_frequency: int = 5, num_classes: int = 20,
           start_epoch: int = 1, best_val_loss_init: float = None, best_map_init: float = None, scaler=None,
-          seed: int | None = None, record: dict | None = None, ema=None, accum_steps: int = 1) -> dict[str, float]:
+          seed: int | None = None, record: dict | None = None, ema=None, accum_steps: int = 1, warmup_steps: int = 0) -> dict[str, float]:
     """Epoch loop with the reference's checkpoint policy: latest every epoch, every ``save_frequency``
     epochs, best validation loss, best mAP50:95.
 
@@ -178,7 +216,9 @@ def train(model, train_loader, val_loader, criterion, optimizer, scheduler, devi
     follow the averaged weights.  Every checkpoint then carries them next to the raw ones (checkpoints.py).  With several ranks each keeps its own
     average; they are identical because the parameters are, and nothing is communicated.
 
-    ``accum_steps``: batches per optimizer step (``train_epoch``)."""
+    ``accum_steps``: batches per optimizer step (``train_epoch``).  ``warmup_steps``: linear learning-rate warm-up over the run's first optimizer
+    steps (``LRWarmup``); a run resumed at ``start_epoch`` continues where the warm-up stood."""
+    warmup = make_warmup(optimizer, warmup_steps, start_epoch, train_loader, accum_steps)
     best_val = float("inf") if best_val_loss_init is None else best_val_loss_init
     best_map = 0.0 if best_map_init is None else best_map_init
     final_train = None
@@ -186,7 +226,7 @@ def train(model, train_loader, val_loader, criterion, optimizer, scheduler, devi
         print(f"\n===== Epoch {epoch}/{num_epochs} =====")
         if seed is not None:
             seed_epoch(seed, epoch, train_loader)
-        tr = train_epoch(model, train_loader, criterion, optimizer, device, epoch, writer, scaler, ema=ema, accum_steps=accum_steps)
+        tr = train_epoch(model, train_loader, criterion, optimizer, device, epoch, writer, scaler, ema=ema, accum_steps=accum_steps, **({"warmup": warmup} if warmup is not None else {}))
         print("  train:", {k: round(v, 4) for k, v in tr.items()})
         want_map = compute_map and (epoch % map_frequency == 0 or epoch == num_epochs)
         va = validate(model if ema is None else ema.module, val_loader, criterion, device, compute_map=want_map, num_classes=num_classes)
