@@ -221,7 +221,8 @@ int yolo_igemm_finish(const yolo_igemm_desc *d, const float *acc, const float *b
  * |tapoff| elements before and after the buffer.  dw is fp32 in the packed layout
  * [Cout][KH*KW][Cin]; with split > 1 or accumulate != 0 it is accumulated with fp32 atomics
  * (caller zero-fills / owns the previous value).  db[co] += sum_p dy[p][co] if db != NULL
- * (always accumulated: caller zero-fills).  Replaces the weight / bias gradient of aten
+ * (always accumulated: caller zero-fills).  dw == NULL: the bias gradient alone, flat indexing only
+ * (with a pixel geometry: YOLO_E_UNSUPPORTED).  Replaces the weight / bias gradient of aten
  * convolution_backward and addmm backward. */
 typedef struct yolo_wgrad_desc {
     int64_t P;                       /* dy pixel slots                                            */
@@ -237,7 +238,9 @@ typedef struct yolo_wgrad_desc {
     int32_t variant;                 /* 0: choose; 1: 128x128 tile, 4 waves, 2 stages; 2: 256x128 tile, 8 waves, 3 stages;
                                         3: 2 + staggered two-phase schedule; 4: 128x128 tile, 8 waves; 5: 256x256 tile, wave
                                         tile 128x64, four 32-pixel stages, register-pipelined one-barrier loop
-                                        (wgrad_pipe.hip; Cin in {64, 128}: 256 / Cin taps per tile); 6: the tiles and schedule of
+                                        (wgrad_pipe.hip; Cin in {8, 16, 32, 64, 128} with KH * KW > 1: 256 / Cin taps per tile, any other
+                                        Cin one tap per tile; flat indexing with pad 0 needs P % 32 == 0, else YOLO_E_UNSUPPORTED: rows past
+                                        the range re-read slot 0, which must be a zero halo slot of dy); 6: the tiles and schedule of
                                         5 with FOUR waves of 128x128, one per SIMD, 256 accumulator registers in AGPRs
                                         (wgrad_wide.hip)  (tests / tuning; all agree bit for bit with one pixel range per tile)  */
     /* Pixel geometry (geo_W == 0: "flat" indexing, p IS the slot).  Otherwise the reduction runs over the P = N*geo_H*geo_W

@@ -10,6 +10,9 @@ igemm_ref(...) evaluates every output element the descriptor addresses in fp64 f
 
 (one bf16 rounding plus the worst case of an fp32 sum of Ktot products, by Cauchy-Schwarz); a pooled element takes the largest bound of its window.
 
+wgrad_ref(...) is the fp64 weight and bias gradient of one yolo_wgrad launch, wgrad_bound(...) its element bound gamma(P + ranges - 1 + a) sum |dy| |x|
+(fp32 additions of exact products; 0 for operands whose partial sums are all representable).
+
 Below them: BatchNorm forward / backward in training mode (bn.hip) and the pools (pool.hip) on logical NHWC fp64 views, each with a per-element
 bound derived from the kernel's arithmetic (check_values compares any region against such a reference).
 """
@@ -25,6 +28,7 @@ import torch.nn.functional as F
 EPI_NONE, EPI_BIAS, EPI_BIAS_LRELU, EPI_MUL_DLRELU, EPI_BIAS_ADD_LRELU = 0, 1, 2, 3, 4
 CHUNK_BYTES = 256 << 20       # fp64 im2col rows per matmul (the patches of one image at least)
 TINY = 2.0 ** -126
+U = 2.0 ** -24                # unit roundoff of fp32
 
 
 def _g(d, name, default=0):
@@ -241,9 +245,10 @@ def wgrad_extent(d, what: str):
     raise ValueError(what)
 
 
-def wgrad_ref(d, x, x_base, dy, dy_base=0, device=None):
+def wgrad_ref(d, x, x_base, dy, dy_base=0, device=None, absolute=False):
     """fp64 (dw [Cout][KH*KW*Cin], db [Cout]) of one yolo_wgrad launch, WITHOUT the previous contents of dw / db (the caller adds them where the
-    launch accumulates).  dw[co][tap][ci] = sum_p dy[slot(p) * dy_px_stride + co] * x[slot(p) * x_px_stride + tapoff(tap) + ci]."""
+    launch accumulates).  dw[co][tap][ci] = sum_p dy[slot(p) * dy_px_stride + co] * x[slot(p) * x_px_stride + tapoff(tap) + ci].
+    absolute: -> (dw, db, S_dw, S_db) with S the same sums over |dy| and |x| (one more matmul per chunk): the scale of wgrad_bound"""
     dev = device if device is not None else x.device
     dims, slots, slot0 = _wgrad_pixels(d)
     Co, Ci, KH, KW, pad = _g(d, "Cout"), _g(d, "Cin"), _g(d, "KH"), _g(d, "KW"), _g(d, "pad")
@@ -251,6 +256,7 @@ def wgrad_ref(d, x, x_base, dy, dy_base=0, device=None):
     K = KH * KW * Ci
     dw = torch.zeros(Co, K, dtype=torch.float64, device=dev)
     db = torch.zeros(Co, dtype=torch.float64, device=dev)
+    adw, adb = (torch.zeros_like(dw), torch.zeros_like(db)) if absolute else (None, None)
     outer, inner = dims[0], dims[1:]
     n_inner = math.prod(inner) if inner else 1
     step = max(1, CHUNK_BYTES // max(1, n_inner * (K + Co) * 8))
@@ -265,7 +271,57 @@ def wgrad_ref(d, x, x_base, dy, dy_base=0, device=None):
         X = X.to(dev, torch.float64).reshape(-1, K)
         dw += G.T @ X
         db += G.sum(0)
-    return dw, db
+        if absolute:
+            G.abs_()
+            X.abs_()
+            adw += G.T @ X
+            adb += G.sum(0)
+    return (dw, db, adw, adb) if absolute else (dw, db)
+
+
+def gamma(n) -> float:
+    """Higham's gamma_n = n u / (1 - n u) for fp32: the relative error bound of any n chained roundings, second-order terms included (n u < 1)"""
+    nu = n * U
+    assert nu < 1.0, n
+    return nu / (1.0 - nu)
+
+
+def wgrad_bound(d, x, x_base, dy, dy_base=0, dw0=None, db0=None, ranges=None, exact=False, device=None, refs=None):
+    """Value and element bound of one yolo_wgrad launch: -> namespace (dw, dw_bnd [Cout * KH*KW*Cin], db, db_bnd [Cout], n).
+
+    The operands are bf16, so every product dy * x is exact in fp32 (8 + 8 significand bits) and the only roundings are fp32 additions.  An output
+    element is the sum of P products, added in some tree inside the MFMA accumulation of a pixel range, plus the additions that join the R pixel
+    ranges of a tile (atomics or the slab sum), plus one onto the previous contents where the launch accumulates.  No term passes more than
+        n = P + R - 1 + a
+    additions whatever the tree or the order, each relative to a partial sum of magnitude <= S = sum_p |dy| |x| (+ |dw0|), so
+        |dw - ref| <= gamma(n) (S + |dw0|),     gamma(n) = n u / (1 - n u),  u = 2^-24
+    and the same for db with x = 1 (the bf16 -> fp32 conversion is exact).  R = `ranges` (the schedule's exact value), else d.split, else 512 (the
+    workgroup slots: the library never splits a tile finer).  dw0 / db0: previous contents (flat fp tensors) where the launch adds onto them, None
+    where it stores.  refs: wgrad_ref(..., absolute=True) of the same problem, computed once for several modes.  exact: the operands make every
+    partial sum representable (see tests/wgrad_cases.py), so the bound is 0: bit equality.
+
+    Measured on an MI355X: the sum of TWO products comes back up to 1.5 u |sum| off, so the MFMA does not round its internal additions to nearest,
+    and the model of one u per addition has the least room at the smallest P: worst |err| / bound 0.76 - 0.99 at P = 2, 0.46 at P = 3, 0.34 at
+    P = 4, 0.15 at P = 8, about 0.01 from a hundred pixels on."""
+    dev = device if device is not None else x.device
+    dw, db, S, Sb = refs if refs is not None else wgrad_ref(d, x, x_base, dy, dy_base, device=dev, absolute=True)
+    dw, S = dw.reshape(-1), S.reshape(-1)
+    R = int(ranges) if ranges else (_g(d, "split") if _g(d, "split") > 0 else 512)
+    out = SimpleNamespace()
+    n = out.n = _g(d, "P") + R - 1
+    if dw0 is not None:
+        dw0 = dw0.to(dev, torch.float64).reshape(-1)
+        dw, S = dw + dw0, S + dw0.abs()
+    if db0 is not None:
+        db0 = db0.to(dev, torch.float64).reshape(-1)
+        db, Sb = db + db0, Sb + db0.abs()
+    out.dw, out.db = dw, db
+    if exact:
+        out.dw_bnd, out.db_bnd = torch.zeros_like(S), torch.zeros_like(Sb)
+    else:
+        out.dw_bnd = gamma(n + (dw0 is not None)) * S
+        out.db_bnd = gamma(n + (db0 is not None)) * Sb
+    return out
 
 
 def rel_l2(got, ref) -> float:
@@ -284,9 +340,6 @@ def weight_matrix(w, Co, K, blocked=False):
 
 
 # ---- element-wise check of any launch ------------------------------------------------------------------------------------------------------------
-
-U = 2.0 ** -24          # unit roundoff of fp32
-
 
 def check_values(ref, bnd, got, tag, fails, what=""):
     """ref / bnd fp64 over a region, got the region as stored: bnd < 0 not checked, bnd == 0 equal to ref (ref is then the value as stored),

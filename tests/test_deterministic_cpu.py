@@ -10,6 +10,8 @@ import sys
 import pytest
 import torch
 
+import wgrad_cases as wc
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(ROOT, "yolo-v1_amd")
 
@@ -85,29 +87,17 @@ def _conv_layers():
     return out
 
 
+def _schedule(P, Cout, Cin, K, variant=0, x_px_stride=None):
+    """the two-segment schedule of yolo_wgrad (split = 0) restated -> (main_tiles, main_split, tail_tiles, tail_split): 128 x 128 tiles on 512
+    workgroup slots for variants 0 / 1 / 4, 256 x 256 tiles (tile_taps taps each) on 256 slots for variants 5 / 6 (tests/wgrad_cases.py)"""
+    tiles, slots = wc.wgrad_tiles(Cout, Cin, K * K, variant, x_px_stride)
+    return wc.wgrad_schedule(P, tiles, slots)
+
+
 def _some_tile_is_split(P, Cout, Cin, K):
-    """the two-segment schedule of yolo_wgrad (split = 0, 128 x 128 tiles, 512 workgroup slots) restated: does the main or the tail segment use more
-    than one pixel range?"""
-    ntaps = K * K
-    pair = Cin == 64 and ntaps > 1
-    tiles = -(-Cout // 128) * -(-Cin // 128) * ((ntaps + 1) // 2 if pair else ntaps)
-    steps, slots, E = -(-P // 64), 512, 30.0
-    best, bs, bt = 1e30, 1, 1
-    sp = 1
-    while sp <= slots:
-        if sp > 1 and steps // sp < 4:
-            break
-        tpr = slots // sp
-        mt = tiles // tpr * tpr
-        tt = tiles - mt
-        ts = max(sp, min(slots // tt, max(1, steps // 4))) if tt > 0 else 1
-        cost = (mt // tpr) * (-(-steps // sp) + E) + ((-(-steps // ts) + E) if tt > 0 else 0.0)
-        if cost < best:
-            best, bs, bt = cost, sp, ts
-        sp *= 2
-    tpr = slots // bs
-    main_tiles = tiles // tpr * tpr
-    return (main_tiles > 0 and bs > 1) or (tiles - main_tiles > 0 and bt > 1)
+    """does the main or the tail segment of the 128 x 128 kernels' schedule use more than one pixel range?"""
+    main_tiles, main_split, tail_tiles, tail_split = _schedule(P, Cout, Cin, K)
+    return (main_tiles > 0 and main_split > 1) or (tail_tiles > 0 and tail_split > 1)
 
 
 def _lib():

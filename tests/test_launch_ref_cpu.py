@@ -1,6 +1,6 @@
 """The fp64 launch reference of tests/launch_ref.py against stock torch on small problems (no GPU): forward convs at stride 1 / 2 with padded channel
-strides, the parity classes of a stride-2 data gradient, every epilogue, the fused pool and its arg-max codes, both weight-gradient forms -- and three
-sabotaged outputs the checker must reject."""
+strides, the parity classes of a stride-2 data gradient, every epilogue, the fused pool and its arg-max codes, both weight-gradient forms -- and sabotaged
+outputs the checkers must reject (three forward ones, four of a weight gradient that relative L2 lets pass)."""
 
 from types import SimpleNamespace
 
@@ -256,6 +256,58 @@ def test_checker_rejects_sabotaged_outputs():
     lr._out_view(stale, d)[0, 2:4] = lr._out_view(old, d)[0, 2:4]      # flattened output pixels 16 .. 31 keep what the buffer held before
     fails = R.check(stale, what="tile")[1]
     assert fails and "outside their bound" in fails[0]
+    for smooth in (False, True):
+        _wgrad_sabotage(smooth)
+
+
+def _wgrad_sabotage(smooth):
+    """Four ways a weight gradient can be subtly wrong in an otherwise correct result -- one pixel dropped, one tap shifted by a pixel, two input
+    channels swapped, one db element missing one pixel -- over P = 1536 interior pixels (3x3, 16 <- 16 channels).  The element check of
+    launch_ref.wgrad_bound flags each of them, on zero-mean noise and on smooth operands.
+
+    Relative L2 at 1e-3 (all tests/test_gpu_plan_table.py asked of a weight gradient) sees a wrong fraction f of zero-mean terms as sqrt(f) and does
+    flag these on noise.  On smooth operands -- activations and gradients with a common sign and 3 % variation, as behind a LeakyReLU; x zero on the
+    outer ring of the image so that a shifted tap still meets every pixel -- an element is P times a mean, a lost pixel changes it by 1 / P = 6.5e-4,
+    a shifted tap or swapped channel by the variation only, and relative L2 passes all four.  That gap is what the element check closes."""
+    N, H, cin, cout = 6, 16, 16, 16
+    g = torch.Generator().manual_seed(90 + smooth)
+    xb, gb = Buf(N, H, H, cin), Buf(N, H, H, cout)
+    if smooth:
+        xv = 1.0 + 0.03 * torch.randn(N, H, H, cin, generator=g)
+        xv[:, 0], xv[:, -1], xv[:, :, 0], xv[:, :, -1] = 0, 0, 0, 0
+        gv = 0.1 * (1.0 + 0.03 * torch.randn(N, H, H, cout, generator=g))
+    else:
+        xv, gv = torch.randn(N, H, H, cin, generator=g), 0.1 * torch.randn(N, H, H, cout, generator=g)
+    xb.interior().copy_(xv.to(BF))
+    gb.interior().copy_(gv.to(BF))
+    d = SimpleNamespace(P=N * H * H, dy_px_stride=gb.px, x_px_stride=xb.px, Cout=cout, Cin=cin, KH=3, KW=3, pad=1, x_row_stride=xb.row, split=1, accumulate=0,
+                        geo_W=H, geo_H=H, geo_img_slots=xb.Hp * xb.Wp, geo_row_slots=xb.Wp, geo_px_slots=1, geo_slot0=xb.Wp + 1)
+    b = lr.wgrad_bound(d, xb.store, xb.guard, gb.store, gb.guard)
+    assert b.n == d.P
+
+    def flagged(dw, db):
+        fails = []
+        lr.check_values(b.dw, b.dw_bnd, dw.float(), "dw", fails)
+        lr.check_values(b.db, b.db_bnd, db.float(), "db", fails)
+        return bool(fails), max(lr.rel_l2(dw.float(), b.dw), lr.rel_l2(db.float(), b.db))
+
+    hit, l2 = flagged(b.dw, b.db)
+    assert not hit and l2 < 1e-7                                # the fp32 rounding of the reference passes
+    dw3 = b.dw.view(cout, 9, cin)
+    px = gb.interior()[2, 5, 7].clone()
+    gb.interior()[2, 5, 7] = 0
+    no_pixel = lr.wgrad_ref(d, xb.store, xb.guard, gb.store, gb.guard)[0].reshape(-1)
+    gb.interior()[2, 5, 7] = px
+    shifted = dw3.clone()
+    shifted[:, 0] = dw3[:, 1]                                   # tap (0, 0) computed one pixel to the right: the values of tap (0, 1)
+    swapped = dw3.clone()
+    swapped[:, :, 3], swapped[:, :, 5] = dw3[:, :, 5], dw3[:, :, 3]
+    db_short = b.db.clone()
+    db_short[3] -= px[3].double()
+    for name, dw, db in (("pixel", no_pixel, b.db), ("tap", shifted.reshape(-1), b.db), ("channels", swapped.reshape(-1), b.db), ("db", b.dw, db_short)):
+        hit, l2 = flagged(dw, db)
+        assert hit, (name, smooth)
+        assert (l2 < 1e-3) == smooth, (name, smooth, l2)
 
 
 def test_blocked_weight_panels_are_the_linear_weight():

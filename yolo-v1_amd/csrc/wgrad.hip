@@ -1244,7 +1244,9 @@ static int wgrad_run(const yolo_wgrad_desc *d, const void *x, const void *dy, fl
                 return fail(YOLO_E_UNSUPPORTED, "yolo_wgrad: variant 5 addresses operands below 4 GB with fewer than 2^24 pixel slots");
             if (d->geo_W == 0 && d->pad == 0 && d->KH * d->KW == 1 && (d->P % 32))
                 return fail(YOLO_E_UNSUPPORTED, "yolo_wgrad: variant 5 needs zero-haloed operands or P %% 32 == 0");
-            p.tile_taps = (d->Cin < 256 && 256 % d->Cin == 0 && p.ntaps > 1 && d->x_px_stride >= d->Cin) ? 256 / d->Cin : 1;
+            // taps per tile: the kernels place a tap's columns as whole 16-B chunks (Cin / 8 per tap), so Cin must be a multiple of 8 --
+            // Cin in {8, 16, 32, 64, 128}; Cin in {1, 2, 4} would divide by zero chunks per tap and takes one tap per tile like any other Cin
+            p.tile_taps = (d->Cin < 256 && 256 % d->Cin == 0 && d->Cin % 8 == 0 && p.ntaps > 1 && d->x_px_stride >= d->Cin) ? 256 / d->Cin : 1;
             p.n_co_tiles = (d->Cout + 255) / 256;
             p.n_ci_tiles = p.tile_taps > 1 ? 1 : (d->Cin + 255) / 256;
             tiles = p.n_co_tiles * p.n_ci_tiles * ((p.ntaps + p.tile_taps - 1) / p.tile_taps);
@@ -1386,6 +1388,8 @@ static int wgrad_run(const yolo_wgrad_desc *d, const void *x, const void *dy, fl
         }
     }
     if (db && !dw) {
+        // the column sum walks slots 0 .. P - 1: with a pixel geometry it would add other slots than the descriptor names
+        if (d->geo_W != 0) return fail(YOLO_E_UNSUPPORTED, "yolo_wgrad: the bias-only launch (dw == NULL) has no pixel-geometry mode");
         const int nchunks = (d->Cout + 7) / 8;
         const int w = nchunks < 256 ? nchunks : 256;
         const int R = 256 / w;

@@ -8,7 +8,8 @@
 //   * register pipelining inside the wave: while the MFMAs of a 16-pixel sub-step run, the fragments of the next sub-step
 //     are read into the second register set and the wave's share of the next stage's LDS-DMA is issued between the MFMAs
 //     (sched_group_barrier), as in igemm_pipe.hip.
-// Columns: Cin >= 256 -> one tap per tile (ci tiles of 256); Cin in {64, 128} -> 256 / Cin adjacent taps per tile.
+// Columns: Cin in {8, 16, 32, 64, 128} with several taps -> 256 / Cin adjacent taps per tile (a tap is Cin / 8 whole 16-B chunks of the
+// tile's 32); every other Cin, and every 1x1 launch -> one tap per tile (ci tiles of 256).
 // Pixel indexing (flat / geometry), the two-segment schedule and the XCD map are shared with wgrad.hip (wgrad_common.h).
 #include "wgrad_common.h"
 
