@@ -260,8 +260,8 @@ typedef struct yolo_wgrad_desc {
                                         be zero-filled, and dw is bit-reproducible.  yolo_wgrad_slab_floats gives the size a launch needs.
                                         Variants 0 / 1 / 4 (the 128 x 128 kernels; uniform split and split = 0, pair_taps, pixel geometry): only
                                         the workgroups of a tile that IS split over pixel ranges store a dense 128 x 128 partial; a tile owned by
-                                        one workgroup keeps its direct store.  This replaces the atomicAdd epilogue of wgrad_kernel /
-                                        wgrad8_kernel.  With slabs in use, db is order-fixed too: the bias sums of the pixel ranges are stored
+                                        one workgroup keeps its direct store.  This replaces the atomicAdd epilogue of wgrad_kernel
+                                        (4 and 8 waves).  With slabs in use, db is order-fixed too: the bias sums of the pixel ranges are stored
                                         ([co][range]: behind the tile partials for variants 0 / 1 / 4; in row co of dw, which is free until the
                                         slab sum runs, for 5 / 6 -- KH * KW * Cin must hold the ranges) and added in range order into db by a
                                         plain store, so db need not be zero-filled.  A launch of variant 0 / 1 / 4 without a split tile needs

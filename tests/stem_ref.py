@@ -1,4 +1,4 @@
-"""fp64 references of the 7x7 / stride-2 / pad-3 stem launches (csrc/stem.hip, stem_wgrad_kernel<MODE> of csrc/wgrad.hip) with element-wise error
+"""fp64 references of the 7x7 / stride-2 / pad-3 stem launches (csrc/stem.hip, stem_wgrad_kernel<MODE> of csrc/wgrad_stem.hip) with element-wise error
 bounds, in launch_ref.py's conventions: operands are flat bf16 / fp32 tensors as stored, results are an IgemmRef or (ref, bnd) pairs for check_values.
 
 Forward.  The stem is the yolo_igemm problem the generic path runs: KH 7, KW 8, tap_len 4, stride 2, in_px_stride 4, Cout 64, bias + LeakyReLU, over the
@@ -101,7 +101,7 @@ def stem_fwd_ref(d, xbuf, panel, bias, images=None, device=None) -> lr.IgemmRef:
 # ---- weight gradient ----------------------------------------------------------------------------------------------------------------------------
 
 def wgrad_additions(ntiles, G):
-    """fp32 additions on the longest path to one dw / db element, from stem_wgrad_kernel and stem_wgrad_reduce_kernel (csrc/wgrad.hip).
+    """fp32 additions on the longest path to one dw / db element, from stem_wgrad_kernel and stem_wgrad_reduce_kernel (csrc/wgrad_stem.hip).
     Workgroup g of G walks the tiles g, g + G, ...: at most ceil(ntiles / G).  Per tile an accumulator element receives the 128 pixel products in
     four v_mfma_f32_16x16x32_bf16 (32 products each, added inside the instruction and to the running accumulator: at most 128 additions however
     the instruction orders them); the bias sum takes 32 pixels per lane and tile (pairs first, then the running sum) plus two cross-lane

@@ -101,6 +101,6 @@ def test_inline_assembly_blocks_have_their_wait_states():
     import sys
     if not os.path.exists("/opt/rocm/bin/hipcc") and shutil.which("hipcc") is None:
         pytest.skip("no hipcc")
-    files = [os.path.join(ROOT, "yolo-v1_amd", "csrc", f) for f in ("igemm_persist.hip", "wgrad_wide.hip", "wgrad_pipe.hip")]
+    files = [os.path.join(ROOT, "yolo-v1_amd", "csrc", f) for f in ("igemm_persist.hip", "wgrad_wide.hip", "wgrad_pipe.hip", "wgrad.hip")]
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_asm_hazards.py")] + files, capture_output=True, text=True)
     assert r.returncode == 0 and "inline-assembly hazards: 0" in r.stdout, r.stdout + r.stderr

@@ -1,7 +1,7 @@
 """The 7x7 / stride-2 stem family, launch by launch through the C ABI, against the fp64 references of tests/stem_ref.py:
 
   yolo_conv_stem7_fwd, yolo_conv_stem7_fwd_f32            csrc/stem.hip          (persistent, two-buffer pipeline, stores one iteration late)
-  yolo_wgrad_stem7, yolo_wgrad_stem7_pooled, _codes       csrc/wgrad.hip         (stem_wgrad_kernel<0 / 1 / 2> + stem_wgrad_reduce_kernel)
+  yolo_wgrad_stem7, yolo_wgrad_stem7_pooled, _codes       csrc/wgrad_stem.hip    (stem_wgrad_kernel<0 / 1 / 2> + stem_wgrad_reduce_kernel)
   yolo_maxpool3s2_fwd                                     csrc/pool.hip
 
 Every addressed output element lies within its derived bound (arg-max codes by igemm_ref's rule), the entries that promise equal bits give equal
@@ -23,8 +23,8 @@ import stem_ref as sr
 pytestmark = pytest.mark.gpu
 
 FWD_GRID = 1024      # csrc/stem.hip:332 and :365, yolo_conv_stem7_fwd / _fwd_f32: `const long G = std::min<long>(nt, 1024);`
-WGRAD_GRID = 768     # csrc/wgrad.hip:1163, wgrad_stem7_impl: `long G = std::min<long>(nt, 768);`
-PART = sr.PART       # csrc/wgrad.hip: ST_PART = 64 * ST_COLS + 64 floats per workgroup partial
+WGRAD_GRID = 768     # csrc/wgrad_stem.hip:297, wgrad_stem7_impl: `long G = std::min<long>(nt, 768);`
+PART = sr.PART       # csrc/wgrad_stem.hip: ST_PART = 64 * ST_COLS + 64 floats per workgroup partial
 
 CASES = {
     "A": (1, 16, 32),        # one tile: all four image borders inside it

@@ -1,5 +1,6 @@
-// Pieces shared by the weight-gradient kernels (wgrad.hip, wgrad_pipe.hip): launch parameters and the workgroup -> (tile,
-// pixel range) map of the two-segment schedule.
+// Pieces shared by the weight-gradient kernels.  wgrad.hip (128 x 128 and 256 x 128 tiles, the host side of yolo_wgrad), wgrad_pipe.hip and
+// wgrad_wide.hip (256 x 256 tiles) share the launch parameters and the workgroup -> (tile, pixel range) map of the two-segment schedule;
+// wgrad_stem.hip (the 7x7 stem, its own entry points) only the vector types and the LDS-DMA macro.
 #pragma once
 #include <algorithm>
 #include <type_traits>
@@ -110,6 +111,20 @@ __device__ __forceinline__ long wgrad_slab_index(const WgradParams &p, int part)
 #define GLDS16(gptr, lptr) \
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)(gptr), (__attribute__((address_space(3))) void *)(lptr), 16, 0, 0)
 
+// Two kernels (the forms of one template) that need `bytes` > 64 KB of dynamic LDS.  A function's attributes belong to the device it is
+// loaded on, so success is remembered per device in `done`, the caller's static array.  0 or the failure's code.
+inline int wgrad_lds_attr(bool (&done)[64], const void *k0, const void *k1, int bytes)
+{
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (done[dev]) return 0;
+    hipError_t e = hipFuncSetAttribute(k0, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e == hipSuccess) e = hipFuncSetAttribute(k1, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+    if (e != hipSuccess) return fail((int)e, "yolo_wgrad: hipFuncSetAttribute(%d B LDS): %s", bytes, hipGetErrorString(e));
+    done[dev] = true;
+    return 0;
+}
+
 // wgrad_pipe.hip: 256 x 256 tile, wave tile 128 x 64, register-pipelined one-barrier loop (yolo_wgrad_desc.variant = 5)
 int wgrad_pipe_launch(const WgradParams &p, dim3 grid, hipStream_t s);
 // wgrad_wide.hip: the same tiles and schedule, four waves of 128 x 128 with the accumulators in AGPRs (yolo_wgrad_desc.variant = 6)
@@ -117,7 +132,7 @@ int wgrad_wide_launch(const WgradParams &p, dim3 grid, hipStream_t s);
 // ... slab mode: sum of the partial tiles into the packed gradient (main_ranges / tail_ranges = pixel ranges that hold pixels)
 int wgrad_slab_sum_launch(const WgradParams &p, int tiles, int main_ranges, int tail_ranges, hipStream_t s);
 // ... and of the bias partials (WgradParams.bias_part) into db, in range order; tile_co = rows of a co tile (128 / 256)
-int wgrad_bias_sum_launch(const WgradParams &p, int tile_co, int tiles, int main_ranges, int tail_ranges, float *db, hipStream_t s);
+int wgrad_bias_sum_launch(const WgradParams &p, int tile_co, int main_ranges, int tail_ranges, float *db, hipStream_t s);
 // igemm.hip: the debug buffer of yolo_debug_stamps (diagnostic builds)
 void debug_stamp_target(long **buf, int *it);
 

@@ -505,14 +505,7 @@ int wgrad_slab_sum_launch(const WgradParams &p, int tiles, int main_ranges, int 
 int wgrad_pipe_launch(const WgradParams &p, dim3 grid, hipStream_t s)
 {
     static bool attr_done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void *)wgrad_pipe_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, wp::LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)wgrad_pipe_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, wp::LDS_BYTES);
-        if (e != hipSuccess) return fail((int)e, "yolo_wgrad: hipFuncSetAttribute(%d B LDS): %s", wp::LDS_BYTES, hipGetErrorString(e));
-        attr_done[dev] = true;
-    }
+    if (int rc = wgrad_lds_attr(attr_done, (const void *)wgrad_pipe_kernel<false>, (const void *)wgrad_pipe_kernel<true>, wp::LDS_BYTES)) return rc;
     WgradParams q = p;
     debug_stamp_target(&q.dbg, &q.dbg_it);
     if (p.gW) hipLaunchKernelGGL(wgrad_pipe_kernel<true>, grid, dim3(wp::NTHR), wp::LDS_BYTES, s, q);

@@ -464,14 +464,7 @@ __global__ void __launch_bounds__(ww::NTHR) wgrad_wide_kernel(const WgradParams 
 int wgrad_wide_launch(const WgradParams &p, dim3 grid, hipStream_t s)
 {
     static bool attr_done[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!attr_done[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void *)wgrad_wide_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, ww::LDS_BYTES);
-        if (e == hipSuccess) e = hipFuncSetAttribute((const void *)wgrad_wide_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, ww::LDS_BYTES);
-        if (e != hipSuccess) return fail((int)e, "yolo_wgrad: hipFuncSetAttribute(%d B LDS): %s", ww::LDS_BYTES, hipGetErrorString(e));
-        attr_done[dev] = true;
-    }
+    if (int rc = wgrad_lds_attr(attr_done, (const void *)wgrad_wide_kernel<false>, (const void *)wgrad_wide_kernel<true>, ww::LDS_BYTES)) return rc;
     WgradParams q = p;
     debug_stamp_target(&q.dbg, &q.dbg_it);
     if (p.gW) hipLaunchKernelGGL(wgrad_wide_kernel<true>, grid, dim3(ww::NTHR), ww::LDS_BYTES, s, q);
