@@ -618,6 +618,52 @@ int yolo_grad_accum(float *dst, const float *x, const float *y, long n, float al
 int yolo_grad_accum_multi(const yolo_accum_tensor *t, int count, float alpha, const float *skip_flag, yolo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Factored gradient of a Linear layer (fc_factored.hip / fc_factored.h).  The weight gradient of nn.Linear is the product of two thin
+ * batch factors, G = scale * dy^T x (addmm backward, the FC head of src/yolo/models.py:239-245); for the Linear(50176, 4096) behind
+ * nn.Flatten the factors are 6.9 MB at batch 64 and G is 822 MB.  These entries take the FACTORS in the optimizer slot of the reference's
+ * train step (src/yolo/training/trainer.py:79-95): the norm for clip_grad_norm_ comes from two rows x rows Gram matrices, and the step
+ * kernels rebuild G tile by tile on the matrix cores (v_mfma_f32_32x32x16_bf16, `rows` on the K axis, zero-padded in LDS to the K step of
+ * 16) and apply the element op of yolo_adam_step_multi / yolo_sgd_step_multi to p / m / v straight out of the accumulator registers.  G
+ * never touches memory.  One device function forms the tile product for the gradient entry and both step entries, one multiply applies
+ * `scale`: G is the same bits in all three, for any `workgroups`.  No atomics anywhere: every entry is a function of its inputs alone.
+ * A workgroup owns tiles of 64 x 64 weights; the input-feature index lies on the MFMA column (lane & 31), so that one accumulator
+ * register is two 128-B row segments of p / m / v.  O and I need not be multiples of the tile, rows need not be a multiple of 16.
+ * Every entry: YOLO_E_ARG for a null pointer, rows / O / I < 1, ld_dy < O, ld_x < I, a negative `workgroups`, scratch too small;
+ * YOLO_E_UNSUPPORTED for I % 8 != 0, ld_dy or ld_x not a multiple of 8, dy / x / p / m / v / buf / g_out not 16-B aligned, p_bf16 or the
+ * doubles not 8-B aligned, rows > YOLO_FC_MAX_ROWS (the two K panels of a tile, 128 x (rows + 8) bf16, must fit the 160 KB of LDS).
+ * Everything is checked before the first launch: a refused call launches nothing. */
+#define YOLO_FC_MAX_ROWS 512
+/* Longest fp32 accumulation chain of one Gram entry in yolo_fc_factored_sumsq: the Gram matrices are formed in chunks of this many
+ * columns on the matrix cores, the chunk partials are added in fp64. */
+#define YOLO_FC_GRAM_CHAIN 256
+typedef struct yolo_fc_factors {
+    const void *dy;   /* bf16 [rows][ld_dy], columns 0..O-1 used  */
+    const void *x;    /* bf16 [rows][ld_x],  columns 0..I-1 used  */
+    int32_t rows;     /* factor rows = images (x ranks); any value >= 1, need not be a multiple of the MFMA K step */
+    int32_t O, I;     /* the weight is fp32 [O][I], row-major (the master's layout) */
+    int32_t ld_dy, ld_x;   /* multiples of 8 */
+    float scale;      /* G = scale * dy^T x   (1 / world size under data parallelism) */
+} yolo_fc_factors;
+/* g_out [O][I] fp32 = G: the gradient on request (what autograd's addmm backward would have stored, times scale). */
+int yolo_fc_factored_grad(const yolo_fc_factors *f, float *g_out, yolo_stream_t stream);
+/* *acc += |G|^2 without forming G: |G|^2 = scale^2 * sum_{n,m} (dy_n . dy_m)(x_n . x_m).  Three order-fixed stages, as norm_fixed.hip: one
+ * wave per (factor, 32 x 32 Gram tile, column range) adds its chunks' fp32 MFMA partials in fp64 and stores the tile; the tiles' ranges
+ * are added in rising order per entry, the two Gram entries multiplied and summed per workgroup into a slot; one workgroup adds the slots
+ * in a fixed order, multiplies by scale^2 (double) and adds onto *acc.  scratch: scratch_doubles >= yolo_fc_factored_sumsq_slots doubles,
+ * 8-B aligned, not shared with a launch in flight on another stream. */
+int yolo_fc_factored_sumsq_slots(const yolo_fc_factors *f, long *doubles);
+int yolo_fc_factored_sumsq(const yolo_fc_factors *f, double *scratch, long scratch_doubles, double *acc, yolo_stream_t stream);
+/* yolo_adam_step_multi / yolo_sgd_step_multi for ONE [O][I] parameter whose gradient is given by its factors (same scalars, same folded
+ * clip, skip flag and bf16 shadow; first_step etc. as there).  workgroups > 0: a persistent grid of that many workgroups walks the tiles
+ * (the background form for a second stream); 0: the whole chip.  The result does not depend on `workgroups`. */
+int yolo_adam_step_factored(const yolo_fc_factors *f, float *p, float *exp_avg, float *exp_avg_sq, void *p_bf16, float lr, float beta1,
+                            float beta2, float eps, float weight_decay, long step, const double *norm_sq, float max_norm,
+                            const float *skip_flag, int workgroups, yolo_stream_t stream);
+int yolo_sgd_step_factored(const yolo_fc_factors *f, float *p, float *buf, void *p_bf16, float lr, float momentum, float dampening,
+                           float weight_decay, int nesterov, int first_step, const double *norm_sq, float max_norm,
+                           const float *skip_flag, int workgroups, yolo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Classification pretraining of the YOLOv1 trunk (the paper's first stage: 20 convolutions, an average pool and one Linear layer
  * at 224 x 224).  These three entries EXTEND the reference surface -- mattiaskvist/yolo-v1 has no classifier stage, it downloads
  * torchvision's ImageNet weights -- so each names the stock-torch operation it replaces instead of a reference line.

@@ -13,6 +13,7 @@
 // 48 of them small; one launch per tensor leaves most of the chip idle for most of the step.  The
 // per-tensor table travels in the kernel arguments (<= YOLO_MT_MAX entries per launch), a workgroup
 // owns one MT_CHUNK-element slice of one tensor and finds it by scanning the table's chunk prefix.
+#include "fc_factored.h"
 #include "multi_tensor.h"
 
 #include <cmath>
@@ -124,6 +125,33 @@ __global__ void __launch_bounds__(1024) adam_multi_bg_kernel(const MtTable<yolo_
     mt_walk_bg(tab, chunks, AdamOp{clip_coefficient(norm_sq, max_norm), wd, b1, b2, step_size, inv_bc2_sqrt, eps});
 }
 
+// yolo_adam_step_factored: the gradient of one [O][I] parameter arrives as its two batch factors (fc_factored.h); a lane applies AdamOp::one to
+// the 16 weights of its accumulator registers
+struct AdamFcEpi {
+    AdamOp op;
+    float *p, *m, *v;
+    bf16_t *pb;
+    struct Elem {
+        float p, m, v;
+    };
+    __device__ __forceinline__ void load(long i, Elem &e) const { e.p = p[i]; e.m = m[i]; e.v = v[i]; }
+    __device__ __forceinline__ void finish(long i, float g, Elem &e) const
+    {
+        op.one(e.p, g, e.m, e.v);
+        p[i] = e.p; m[i] = e.m; v[i] = e.v;
+        if (pb) pb[i] = f32_to_bf16(e.p);
+    }
+};
+
+template <int TEAMS>
+__global__ void __launch_bounds__(256 * TEAMS) adam_fc_kernel(const FcTiles f, float *p, float *m, float *v, bf16_t *pb, float b1, float b2, float eps, float wd,
+                                                      float step_size, float inv_bc2_sqrt, const double *__restrict__ norm_sq, float max_norm,
+                                                      const float *__restrict__ skip_flag)
+{
+    if (mt_skipped(skip_flag)) return;
+    fc_walk_tiles<TEAMS>(f, AdamFcEpi{AdamOp{clip_coefficient(norm_sq, max_norm), wd, b1, b2, step_size, inv_bc2_sqrt, eps}, p, m, v, pb});
+}
+
 __global__ void scale_by_clip_kernel(float *__restrict__ g, long n, const double *__restrict__ norm_sq, float max_norm)
 {
     const float c = clip_ratio(norm_sq, max_norm);
@@ -229,6 +257,30 @@ YOLO_API int yolo_adam_step_multi_bg(const yolo_adam_tensor *t, int count, float
     hipLaunchKernelGGL(adam_multi_bg_kernel, dim3(bg.grid), dim3(1024), BG_LDS, STRM(stream), bg.tab, bg.chunks, beta1, beta2, eps, weight_decay, a.step_size,
                        a.inv_bc2_sqrt, norm_sq, max_norm, skip_flag);
     return check_launch(who);
+}
+
+// yolo_adam_step_factored (the entry stands with the other factored entries in fc_factored.hip; the kernel needs AdamOp)
+int yolo::adam_step_factored(const yolo_fc_factors *d, float *p, float *m, float *v, void *p_bf16, float lr, float beta1, float beta2, float eps,
+                             float weight_decay, long step, const double *norm_sq, float max_norm, const float *skip_flag, int workgroups,
+                             yolo_stream_t stream)
+{
+    const char *who = "yolo_adam_step_factored";
+    if (int rc = fc_check(who, d)) return rc;
+    if (!p || !m || !v || step < 1) return fail(YOLO_E_ARG, "%s: null pointer or step < 1", who);
+    if (fc_misaligned(p, 15) || fc_misaligned(m, 15) || fc_misaligned(v, 15)) return fail(YOLO_E_UNSUPPORTED, "%s: p, exp_avg and exp_avg_sq must be 16-B aligned", who);
+    if (fc_misaligned(p_bf16, 7)) return fail(YOLO_E_UNSUPPORTED, "%s: bf16 shadow is not 8-B aligned", who);
+    if (fc_misaligned(norm_sq, 7)) return fail(YOLO_E_UNSUPPORTED, "%s: norm_sq is not 8-B aligned", who);
+    static bool lds_done[3][64] = {};
+    FcLaunch L;
+    if (int rc = fc_prepare(who, d, workgroups, L)) return rc;
+    const AdamScalars a(lr, beta1, beta2, step);
+    auto launch = [&](auto kernel, bool (&done)[64]) {
+        if (int rc = fc_raise_lds(who, L, (const void *)kernel, done)) return rc;
+        hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(256 * L.teams), L.lds, STRM(stream), L.f, p, m, v, (bf16_t *)p_bf16, beta1, beta2, eps, weight_decay,
+                           a.step_size, a.inv_bc2_sqrt, norm_sq, max_norm, skip_flag);
+        return check_launch(who);
+    };
+    return L.teams == 4 ? launch(adam_fc_kernel<4>, lds_done[2]) : L.teams == 2 ? launch(adam_fc_kernel<2>, lds_done[1]) : launch(adam_fc_kernel<1>, lds_done[0]);
 }
 
 YOLO_API int yolo_clip_scale_f32(float *g, long n, const double *norm_sq, float max_norm, yolo_stream_t stream)

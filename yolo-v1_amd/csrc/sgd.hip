@@ -7,6 +7,7 @@
 // 18 B on the first step (buf is only written), 12 B without momentum (buf is not touched).
 // Same launch shapes as the Adam entries: a workgroup owns one MT_CHUNK slice of one tensor of the table in the kernel arguments
 // (yolo_sgd_step, yolo_sgd_step_multi), or `workgroups` persistent 1024-thread workgroups walk the chunk list (yolo_sgd_step_multi_bg).
+#include "fc_factored.h"
 #include "multi_tensor.h"
 
 namespace yolo {
@@ -101,6 +102,38 @@ __global__ void __launch_bounds__(1024) sgd_multi_bg_kernel(const MtTable<yolo_s
     mt_walk_bg(tab, chunks, SgdOp<MODE>{clip_coefficient(a.norm_sq, a.max_norm), a});
 }
 
+// yolo_sgd_step_factored: the gradient of one [O][I] parameter arrives as its two batch factors (fc_factored.h); a lane applies sgd1 to the 16
+// weights of its accumulator registers
+template <int MODE>
+struct SgdFcEpi {
+    float clip;
+    const SgdArgs &a;
+    float *p, *buf;
+    bf16_t *pb;
+    struct Elem {
+        float p, b;
+    };
+    __device__ __forceinline__ void load(long i, Elem &e) const
+    {
+        e.p = p[i];
+        e.b = MODE == MOM_NEXT ? buf[i] : 0.0f;
+    }
+    __device__ __forceinline__ void finish(long i, float g, Elem &e) const
+    {
+        sgd1<MODE>(e.p, g, e.b, clip, a);
+        p[i] = e.p;
+        if (MODE != MOM_NONE) buf[i] = e.b;
+        if (pb) pb[i] = f32_to_bf16(e.p);
+    }
+};
+
+template <int MODE, int TEAMS>
+__global__ void __launch_bounds__(256 * TEAMS) sgd_fc_kernel(const FcTiles f, float *p, float *buf, bf16_t *pb, const SgdArgs a)
+{
+    if (mt_skipped(a.skip_flag)) return;
+    fc_walk_tiles<TEAMS>(f, SgdFcEpi<MODE>{clip_coefficient(a.norm_sq, a.max_norm), a, p, buf, pb});
+}
+
 }  // namespace yolo
 
 using namespace yolo;
@@ -178,4 +211,35 @@ YOLO_API int yolo_sgd_step_multi_bg(const yolo_sgd_tensor *t, int count, float l
     else if (mode == MOM_FIRST) hipLaunchKernelGGL(sgd_multi_bg_kernel<MOM_FIRST>, grid, block, BG_LDS, STRM(stream), bg.tab, bg.chunks, a);
     else hipLaunchKernelGGL(sgd_multi_bg_kernel<MOM_NEXT>, grid, block, BG_LDS, STRM(stream), bg.tab, bg.chunks, a);
     return check_launch(who);
+}
+
+// yolo_sgd_step_factored (the entry stands with the other factored entries in fc_factored.hip; the kernel needs sgd1)
+int yolo::sgd_step_factored(const yolo_fc_factors *d, float *p, float *buf, void *p_bf16, float lr, float momentum, float dampening, float weight_decay,
+                            int nesterov, int first_step, const double *norm_sq, float max_norm, const float *skip_flag, int workgroups,
+                            yolo_stream_t stream)
+{
+    const char *who = "yolo_sgd_step_factored";
+    if (int rc = fc_check(who, d)) return rc;
+    SgdArgs a;
+    int mode;
+    if (int rc = sgd_args(who, lr, momentum, dampening, weight_decay, nesterov, first_step, norm_sq, max_norm, skip_flag, a, mode)) return rc;
+    if (!p || (mode != MOM_NONE && !buf)) return fail(YOLO_E_ARG, "%s: null pointer", who);
+    if (fc_misaligned(p, 15) || (mode != MOM_NONE && fc_misaligned(buf, 15))) return fail(YOLO_E_UNSUPPORTED, "%s: p and buf must be 16-B aligned", who);
+    if (fc_misaligned(p_bf16, 7)) return fail(YOLO_E_UNSUPPORTED, "%s: bf16 shadow is not 8-B aligned", who);
+    if (fc_misaligned(norm_sq, 7)) return fail(YOLO_E_UNSUPPORTED, "%s: norm_sq is not 8-B aligned", who);
+    FcLaunch L;
+    if (int rc = fc_prepare(who, d, workgroups, L)) return rc;
+    bf16_t *pb = (bf16_t *)p_bf16;
+    static bool lds_done[3][3][64] = {};
+    auto launch = [&](auto kernel, bool (&done)[64]) {
+        if (int rc = fc_raise_lds(who, L, (const void *)kernel, done)) return rc;
+        hipLaunchKernelGGL(kernel, dim3(L.grid), dim3(256 * L.teams), L.lds, STRM(stream), L.f, p, buf, pb, a);
+        return check_launch(who);
+    };
+    auto teams = [&](auto k1, auto k2, auto k4) {
+        return L.teams == 4 ? launch(k4, lds_done[mode][2]) : L.teams == 2 ? launch(k2, lds_done[mode][1]) : launch(k1, lds_done[mode][0]);
+    };
+    if (mode == MOM_NONE) return teams(sgd_fc_kernel<MOM_NONE, 1>, sgd_fc_kernel<MOM_NONE, 2>, sgd_fc_kernel<MOM_NONE, 4>);
+    if (mode == MOM_FIRST) return teams(sgd_fc_kernel<MOM_FIRST, 1>, sgd_fc_kernel<MOM_FIRST, 2>, sgd_fc_kernel<MOM_FIRST, 4>);
+    return teams(sgd_fc_kernel<MOM_NEXT, 1>, sgd_fc_kernel<MOM_NEXT, 2>, sgd_fc_kernel<MOM_NEXT, 4>);
 }

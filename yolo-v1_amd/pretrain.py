@@ -95,6 +95,10 @@ def main():
     ap.add_argument("--batch-norm", action="store_true",
                     help="Conv2d(bias=False) + BatchNorm2d + LeakyReLU(0.1) in place of Conv2d + LeakyReLU(0.1) on every convolution of the YOLOv1 network (Darknet's "
                          "batch_normalize=1): trains from the default initialisation.  Recorded in the checkpoint; --resume and --backbone-weights check it")
+    ap.add_argument("--factored-fc", action="store_true",
+                    help="EngineConfig.FC_FACTORED: the weight gradient of a Linear layer with at least FC_FACTORED_MIN weights (the Linear(50176, 4096) behind "
+                         "nn.Flatten) is never stored: the update kernel of --optimizer adam / sgd rebuilds it from its two batch factors, and several ranks "
+                         "all-gather 7 MB of factors instead of all-reducing 822 MB.  Not with --optimizer lars, --accum-steps > 1 or --device cpu")
     a = ap.parse_args()
     if bool(a.synthetic) == bool(a.data_root):
         ap.error("give exactly one of --data-root and --synthetic")
@@ -102,6 +106,15 @@ def main():
         ap.error("--label-smoothing must lie in [0, 1)")
     if a.accum_steps < 1:
         ap.error("--accum-steps must be at least 1")
+    if a.factored_fc:
+        if a.optimizer == "lars":
+            ap.error("--factored-fc is not supported with --optimizer lars (the trust ratio needs the gradient's per-tensor norm): use adam or sgd")
+        if a.accum_steps > 1:
+            ap.error("--factored-fc is not supported with --accum-steps > 1 (the sum of K factored gradients is not one product of two factors)")
+        if not str(a.device).startswith("cuda"):
+            ap.error("--factored-fc is not supported with --device cpu (the factored update runs in the HIP kernels only)")
+        from yolo.config import CONFIG as _cfg
+        _cfg.FC_FACTORED = True
     if a.optimizer == "lars" and a.nesterov:
         ap.error("--optimizer lars has no Nesterov momentum (--nesterov is --optimizer sgd only)")
     if a.warmup_steps < 0:

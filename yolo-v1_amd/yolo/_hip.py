@@ -93,6 +93,17 @@ class LarsTensor(ctypes.Structure):
                 ("adapt", ctypes.c_int)]
 
 
+class FcFactors(ctypes.Structure):
+    """struct yolo_fc_factors (include/yolo_hip.h): the two batch factors of a Linear layer's weight gradient, G = scale * dy^T x."""
+
+    _fields_ = [("dy", c_void_p), ("x", c_void_p), ("rows", ctypes.c_int32), ("O", ctypes.c_int32), ("I", ctypes.c_int32),
+                ("ld_dy", ctypes.c_int32), ("ld_x", ctypes.c_int32), ("scale", ctypes.c_float)]
+
+
+FC_MAX_ROWS = 512            # YOLO_FC_MAX_ROWS
+FC_GRAM_CHAIN = 256          # YOLO_FC_GRAM_CHAIN: longest fp32 chain of a Gram entry in yolo_fc_factored_sumsq
+
+
 class EmaTensor(ctypes.Structure):
     """struct yolo_ema_tensor (include/yolo_hip.h)."""
 
@@ -219,6 +230,13 @@ _SIGS = {
     "yolo_ema_update_multi_bg": [ctypes.POINTER(EmaTensor), c_int, c_float, c_void_p, c_int, c_void_p],
     "yolo_grad_accum": [c_void_p, c_void_p, c_void_p, c_long, c_float, c_void_p, c_void_p],
     "yolo_grad_accum_multi": [ctypes.POINTER(AccumTensor), c_int, c_float, c_void_p, c_void_p],
+    "yolo_fc_factored_grad": [ctypes.POINTER(FcFactors), c_void_p, c_void_p],
+    "yolo_fc_factored_sumsq_slots": [ctypes.POINTER(FcFactors), ctypes.POINTER(c_long)],
+    "yolo_fc_factored_sumsq": [ctypes.POINTER(FcFactors), c_void_p, c_long, c_void_p, c_void_p],
+    "yolo_adam_step_factored": [ctypes.POINTER(FcFactors), c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_float, c_long, c_void_p,
+                                c_float, c_void_p, c_int, c_void_p],
+    "yolo_sgd_step_factored": [ctypes.POINTER(FcFactors), c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_float, c_int, c_int, c_void_p, c_float,
+                               c_void_p, c_int, c_void_p],
     "yolo_gap_fwd": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "yolo_gap_bwd": [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p],
     "yolo_softmax_xent_fwd_bwd": [c_void_p, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],

@@ -40,6 +40,10 @@ class EngineConfig:
     POOL_CODES: bool = True          # training: a fused conv + pool stores the pooled map and 2-bit arg-max codes, not the un-pooled activation
     FUSE_POOL: bool = True           # inference: fold MaxPool2d(2,2) into the preceding conv's epilogue where the geometry allows
     FC_NORM_IN_WGRAD: int = 1 << 26  # Linear layers with at least this many weights: yolo_wgrad also sums the squares of the gradient it stores
+    FC_FACTORED: bool = False        # Linear layers with at least FC_FACTORED_MIN weights keep their weight gradient FACTORED: no yolo_wgrad launch for dw, weight.grad stays None,
+                                     # the plan records the two batch factors (Plan.fc_factors) and yolo.optim.Adam / SGD rebuild the gradient tile by tile inside the update
+                                     # kernel (yolo_adam_step_factored / yolo_sgd_step_factored): 822 MB less to store, to read and to all-reduce per step
+    FC_FACTORED_MIN: int = 1 << 26   # ... the minimum weight count, as FC_NORM_IN_WGRAD: only the Linear behind nn.Flatten qualifies (tests lower it)
     # ---- the schedule of the backward pass
     WGRAD_STREAM: bool = True        # weight gradients run on a second HIP stream beside the data-gradient chain (they are off its critical path)
     SIDE_LOW: bool = True            # ... of the lowest scheduling priority: the dispatcher prefers the data-gradient chain (12.73 -> 12.55 ms per step)

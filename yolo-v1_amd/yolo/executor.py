@@ -19,6 +19,7 @@ Everything is enqueued on the current PyTorch stream (and the plan's side stream
 from __future__ import annotations
 
 import ctypes
+import weakref
 from dataclasses import dataclass
 
 import torch
@@ -54,6 +55,35 @@ class Layer:
     Wout: int = 0
 
 
+class FcFactors:
+    """The pending weight gradient of one Linear layer as its two batch factors (EngineConfig.FC_FACTORED): G = scale * dy[:, :O]^T x, with
+    ``dy`` bf16 [rows][ld_dy] (the gradient wrt the layer's output, through its dropout + LeakyReLU) and ``x`` bf16 [rows][ld_x] (the layer's
+    input).  The record OWNS both tensors: ``x`` is a copy of the workspace's flatten buffer, which the next forward rewrites while a
+    background optimizer pass may still read the factors.  ``parallel.gather_fc_factors`` replaces it by the ranks' concatenation with
+    ``scale = 1 / world``."""
+
+    __slots__ = ("dy", "x", "rows", "scale")
+
+    def __init__(self, dy: torch.Tensor, x: torch.Tensor, rows: int, scale: float = 1.0):
+        self.dy, self.x, self.rows, self.scale = dy, x, int(rows), float(scale)
+
+    def desc(self, weight) -> "_hip.FcFactors":
+        """struct yolo_fc_factors for the [O][I] parameter ``weight``"""
+        O, I = weight.shape
+        return _hip.FcFactors(self.dy.data_ptr(), self.x.data_ptr(), self.rows, O, I, self.dy.stride(0), self.x.stride(0), self.scale)
+
+    def nbytes(self) -> int:
+        return self.dy.numel() * self.dy.element_size() + self.x.numel() * self.x.element_size()
+
+
+def fc_factors_of(p):
+    """the pending FcFactors record of parameter ``p`` (None: it has an ordinary gradient or none) and the plan that holds it"""
+    ref = getattr(p, "_fc_factored_plan", None)
+    plan = ref() if ref is not None else None
+    rec = plan.fc_factors.get(id(p)) if plan is not None else None
+    return (rec, plan) if rec is not None else (None, None)
+
+
 class Plan:
     """Executable plan for [conv|pool]* [flatten fc*]? (with no conv / pool in front, the input is the feature map that nn.Flatten flattens)."""
 
@@ -73,6 +103,7 @@ class Plan:
         self._pd2: dict[int, tuple] = {}
         self._ws: dict[tuple, list] = {}
         self.grad_norm_sq: dict = {}   # id(weight) -> ((data_ptr, shape) of the gradient, its version, device double |g|^2) left by the last backward pass
+        self.fc_factors: dict = {}     # id(weight) -> FcFactors left by the last backward pass (EngineConfig.FC_FACTORED); the optimizer step that consumes a record removes it
         self.debug_keep = False      # tests: True = keep the last workspace (activations + gradients) for inspection AND store the
                                      # un-pooled activations; "codes" = keep the workspace of the product path (pooled maps + arg-max codes)
         self.last = None
@@ -101,7 +132,7 @@ class Plan:
         off = 0
         wv, bv = {}, {}
         for li in order:                          # every view starts on a 256-B boundary (float4 kernels)
-            n = self.layers[li].weight.numel()
+            n = 0 if self._fc_factored(self.layers[li]) else self.layers[li].weight.numel()      # a factored layer has no dw: its factors are gathered instead
             wv[li] = (off, off + n, _round_up(off + n, 64))
             off = _round_up(off + n, 64)
         self._arena_w_end = off
@@ -110,10 +141,27 @@ class Plan:
             bv[li] = (off, off + n)
             off = _round_up(off + n, 64)
         self.arena = torch.zeros(off, dtype=torch.float32, device=device)
-        self.arena_views = {li: (self.arena[wv[li][0]:wv[li][1]].view_as(self.layers[li].weight),
+        self.arena_views = {li: (self.arena[wv[li][0]:wv[li][1]].view_as(self.layers[li].weight) if wv[li][1] > wv[li][0] else None,
                                  self.arena[bv[li][0]:bv[li][1]].view_as(self.layers[li].bias), wv[li][0], wv[li][2])
                             for li in order}
         return self.arena
+
+    def _fc_factored(self, L: Layer) -> bool:
+        """this Linear layer's weight gradient stays factored (EngineConfig.FC_FACTORED; I % 8 == 0 is what the kernels' 16-B operand loads need)"""
+        return bool(self.c.FC_FACTORED) and L.kind == "fc" and L.Cout * L.Cin >= self.c.FC_FACTORED_MIN and L.Cin % 8 == 0
+
+    @_hip.device_guard
+    def fc_weight_grad(self, weight: torch.Tensor) -> torch.Tensor:
+        """the gradient of a factored Linear weight on request (yolo_fc_factored_grad), fp32 in the weight's shape: what ``weight.grad`` would hold.
+        The record stays pending: the optimizer step forms the same bits tile by tile."""
+        rec = self.fc_factors.get(id(weight))
+        if rec is None:
+            raise RuntimeError("Plan.fc_weight_grad: this parameter has no pending factored gradient (EngineConfig.FC_FACTORED off, no backward pass "
+                               "since the last optimizer step, or not a qualifying Linear weight)")
+        g = torch.empty(tuple(weight.shape), dtype=torch.float32, device=rec.dy.device)
+        d = rec.desc(weight)
+        check(RT.lib().yolo_fc_factored_grad(ctypes.byref(d), ptr(g), RT.stream()), "yolo_fc_factored_grad")
+        return g
 
     def _layer_done(self, li: int):
         if self.arena is not None and self.on_grad_ready is not None:
@@ -699,10 +747,22 @@ class Plan:
         check(L_.yolo_scale_rows_to_bf16(ptr(b.g_flat), ptr(mask), ((1.0 / (1.0 - L.dropout)) if L.dropout < 1.0 else 0.0) if mask is not None else 1.0,
                                          ptr(y_act) if (L.lrelu and not last) else None, self.SLOPE, N, L.Cout, ldg, ptr(gb), st), "scale_rows")
         # weight / bias gradient, native [O][K] layout
-        dw, db = b.grad_tensors(li)
+        fact = self._fc_factored(L)
+        dw, db = b.grad_tensors(li, want_dw=not fact)
         wd = WgradDesc(N, ldg, L.Cin, L.Cout, L.Cin, 1, 1, 0, 0, 1, 0)
         nsq = None
-        if det:
+        if fact:
+            # no dw: the optimizer rebuilds it from (gb, xin) inside its update kernel.  The bias gradient still runs (dw == NULL: a column sum of gb).
+            if N > _hip.FC_MAX_ROWS:
+                raise _hip.HipUnsupported(f"EngineConfig.FC_FACTORED: batch {N} exceeds the {_hip.FC_MAX_ROWS} factor rows the update kernels take")
+            nch = (L.Cout + 7) // 8
+            if det and N // ((256 // min(nch, 256)) * 32) > 2:
+                raise NotImplementedError(f"EngineConfig.DETERMINISTIC with EngineConfig.FC_FACTORED at batch {N}: the bias-only yolo_wgrad launch adds more "
+                                          "than two row ranges with atomics there")
+            # the record owns its factors: xin is the workspace's flatten buffer, rewritten by the next forward while a background update may still read it
+            self.fc_factors[id(L.weight)] = FcFactors(gb, xin.clone(), N, 1.0)
+            L.weight._fc_factored_plan = weakref.ref(self)
+        elif det:
             pass      # the norm hint ends in one fp64 atomic per workgroup: the optimizer's order-fixed pass reads this gradient instead
         elif L.Cout * L.Cin >= self.c.FC_NORM_IN_WGRAD and L.Cin % 4 == 0:
             # the kernel that stores this gradient also sums its squares: the optimizer's global-norm pass (clip_grad_norm_) then
@@ -715,9 +775,9 @@ class Plan:
         if side:
             b.fc_keep.append(gb)          # (a temporary of the main stream's allocator that the second stream reads: alive until the streams join)
         with b.on_side(side) as wst:
-            if det:
+            if det and not fact:
                 _attach_wgrad_slabs(L_, wd, dev, wst)
-            with _timed(f"fc{li}.wgrad", "wgrad", 2.0 * N * L.Cout * L.Cin):
+            with _timed(f"fc{li}.wgrad", "wgrad", 2.0 * N * L.Cout * (1 if fact else L.Cin)):
                 check(L_.yolo_wgrad(ctypes.byref(wd), ptr(xin), ptr(gb), ptr(dw), ptr(db), wst), f"wgrad fc{li}")
             self._layer_done(li)
         if nsq is not None:
@@ -1024,14 +1084,16 @@ class _Backward:
         """``with b.on_side() as st:`` -- the second stream, behind everything queued on the main one (the main stream itself without one / if not side)"""
         return _on_side_stream(self.main_t, self.side_t if side else None, self.plan.on_stream_wait if self.plan.arena is not None else None)
 
-    def grad_tensors(self, i: int):
-        """(dw, db) of layer i: the arena's views, or a fresh weight gradient and a slice of the zeroed bias scratch"""
+    def grad_tensors(self, i: int, want_dw: bool = True):
+        """(dw, db) of layer i: the arena's views, or a fresh weight gradient and a slice of the zeroed bias scratch (dw None: a factored Linear layer)"""
         if self.plan.arena is not None:
             dw, db, _, _ = self.plan.arena_views[i]
+            if want_dw != (dw is not None):
+                raise RuntimeError("the gradient arena was attached with another EngineConfig.FC_FACTORED / FC_FACTORED_MIN than this backward pass runs with")
             return dw, db
         L = self.plan.layers[i]
         o = self.offs[("b", i)]
-        return torch.empty_like(L.weight, dtype=torch.float32), self.bscratch[o: o + L.Cout]
+        return (torch.empty_like(L.weight, dtype=torch.float32) if want_dw else None), self.bscratch[o: o + L.Cout]
 
     def flush(self):
         """packed -> OIHW conversion of the finished conv gradients, several layers per launch (yolo_unpack_conv_wgrads_multi) on the current

@@ -25,6 +25,7 @@ import weakref
 from . import _hip
 from ._hip import MT_MAX, AccumTensor, AdamTensor, EmaTensor, SgdTensor, check, lib, ptr, stream
 from .config import CONFIG as CFG
+from .executor import fc_factors_of
 
 
 BG_CUS = 128       # CUs the background update of the Linear layers holds (yolo_adam_step_multi_bg): a CU streams ~42 GB/s whatever it keeps in flight,
@@ -124,6 +125,26 @@ def _split_known(params, known):
     return grads, extra
 
 
+FC_FACTORED_REFUSED = ("EngineConfig.FC_FACTORED (--factored-fc) is not supported with {what}: the factored gradient of the big Linear layer is consumed by "
+                       "the update kernels of yolo.optim.Adam / yolo.optim.SGD only")
+
+
+def _plan_factored(plan) -> bool:
+    cfg = getattr(plan, "c", None)          # (None: not an executor.Plan)
+    return cfg is not None and bool(cfg.FC_FACTORED)
+
+
+def fc_factored_sumsq(weight, rec, acc: torch.Tensor) -> None:
+    """*acc += |G|^2 of the factored gradient ``rec`` of ``weight`` (yolo_fc_factored_sumsq: two Gram matrices, order-fixed, G is not formed),
+    enqueued on the current stream"""
+    d = rec.desc(weight)
+    need = ctypes.c_long(0)
+    check(lib().yolo_fc_factored_sumsq_slots(ctypes.byref(d), ctypes.byref(need)), "yolo_fc_factored_sumsq_slots")
+    st = stream()
+    scratch = _norm_scratch(acc.device, st, need.value)
+    check(lib().yolo_fc_factored_sumsq(ctypes.byref(d), ptr(scratch), scratch.numel(), ptr(acc), st), "yolo_fc_factored_sumsq")
+
+
 def clip_grad_norm_(parameters, max_norm: float) -> torch.Tensor:
     """HIP version of torch.nn.utils.clip_grad_norm_ (L2): returns the total norm as a device tensor."""
     params = [p for p in parameters if p.grad is not None]
@@ -168,10 +189,12 @@ class _Fused(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        all_params = [p for g in self.param_groups for p in g["params"] if p.grad is not None]
+        all_params = [p for g in self.param_groups for p in g["params"] if p.grad is not None or fc_factors_of(p)[0] is not None]
         if not all_params:
             return loss
         if all(not p.is_cuda for p in all_params):
+            if CFG.FC_FACTORED:
+                raise RuntimeError(FC_FACTORED_REFUSED.format(what="CPU parameters"))
             self._step_on_cpu(all_params)
             return loss
         _hip.require_cuda(*all_params)
@@ -189,7 +212,35 @@ class _Fused(torch.optim.Optimizer):
     def _clip_norm_sq(self, all_params):
         """device double with the global squared gradient norm the step launches clip by (None: no clipping), enqueued on the current stream in
         front of the first step launch"""
-        return grad_norm_sq(all_params, self._known_norms()) if self.max_grad_norm is not None else None
+        if self.max_grad_norm is None:
+            return None
+        known = self._known_norms()
+        dense = [p for p in all_params if p.grad is not None]
+        acc = grad_norm_sq(dense, known) if dense else torch.zeros((), dtype=torch.float64, device=all_params[0].device)
+        for p in all_params:
+            # a factored gradient adds its |G|^2 from the Gram matrices of its factors: order-fixed with and without DETERMINISTIC
+            rec, _ = fc_factors_of(p) if p.grad is None else (None, None)
+            if rec is not None:
+                fc_factored_sumsq(p, rec, acc)
+        return acc
+
+    def _enter_side(self, main_t, norm, skip, side_used: bool):
+        """the second stream, behind the gradients, the norm and the last forward's / backward's reads (once per step)"""
+        side = self._side_stream()
+        if not side_used:
+            side.wait_stream(main_t)
+            if norm is not None:
+                norm.record_stream(side)
+            if skip is not None:
+                skip.record_stream(side)
+        return side
+
+    def _factored_state(self, group, p):
+        """the state of a parameter whose gradient is factored, created (and counted up) on the current stream before any launch of the step"""
+        raise RuntimeError(FC_FACTORED_REFUSED.format(what=f"yolo.optim.{type(self).__name__}"))
+
+    def _launch_factored(self, group, p, rec, shadow, fstate, norm, skip, side):
+        raise RuntimeError(FC_FACTORED_REFUSED.format(what=f"yolo.optim.{type(self).__name__}"))
 
     def _step_on_device(self, all_params, loss):
         norm = self._clip_norm_sq(all_params)
@@ -205,8 +256,16 @@ class _Fused(torch.optim.Optimizer):
             # one launch per (group, key of the subclass, foreground / background): normally one for the conv stack and one for the Linear layers
             by_key: dict[tuple, list] = {}
             keep = []                      # temporaries the launch reads must outlive the enqueue
+            factored = []                  # (p, record, its plan, shadow hook, background?, state) of the parameters whose gradient is a pair of factors
             for p in group["params"]:
                 if p.grad is None:
+                    rec, rplan = fc_factors_of(p)
+                    if rec is not None:
+                        if p.dtype != torch.float32 or not p.is_contiguous():
+                            raise RuntimeError(f"yolo.optim.{type(self).__name__} needs contiguous fp32 parameters")
+                        # (the state is created here, on the current stream and in front of the second stream's wait for it: the zero fill of a
+                        # new state tensor must not run beside the background launch that writes it)
+                        factored.append((p, rec, rplan, self.bf16_shadow.get(id(p)), OVERLAP and id(p) in self.deferred, self._factored_state(group, p)))
                     continue
                 if p.dtype != torch.float32 or not p.is_contiguous():
                     raise RuntimeError(f"yolo.optim.{type(self).__name__} needs contiguous fp32 parameters")
@@ -222,14 +281,8 @@ class _Fused(torch.optim.Optimizer):
                 tab = (type(items[0][1]) * len(items))(*[it[1] for it in items])
                 side = None
                 if late and len(items) <= MT_MAX:
-                    side = self._side_stream()
-                    if not side_used:
-                        side.wait_stream(main_t)             # behind the gradients, the norm and the last forward's / backward's reads
-                        if norm is not None:
-                            norm.record_stream(side)
-                        if skip is not None:
-                            skip.record_stream(side)
-                        side_used = True
+                    side = self._enter_side(main_t, norm, skip, side_used)
+                    side_used = True
                 self._launch(group, key, tab, len(items), norm, skip, side)
                 for p, _, hook in items:
                     # the kernel updated p through a raw pointer: bump the autograd version so that the
@@ -237,6 +290,20 @@ class _Fused(torch.optim.Optimizer):
                     torch.autograd.graph.increment_version(p)
                     if hook is not None and hook[1] is not None:
                         hook[1](p)         # ... and tell the owner of a shadow that it is already current
+            for p, rec, rplan, hook, late, fstate in factored:
+                # one launch per factored parameter (yolo_*_step_factored), in the place of its row in the tables above: in the background on
+                # BG_CUS persistent workgroups of the second stream where the parameter is deferred, else on the current stream
+                side = None
+                if late:
+                    side = self._enter_side(main_t, norm, skip, side_used)
+                    side_used = True
+                    rec.dy.record_stream(side)               # the record's own tensors, dropped below: read on the second stream
+                    rec.x.record_stream(side)
+                self._launch_factored(group, p, rec, hook[0] if hook is not None else None, fstate, norm, skip, side)
+                rplan.fc_factors.pop(id(p), None)            # one backward pass feeds one step
+                torch.autograd.graph.increment_version(p)
+                if hook is not None and hook[1] is not None:
+                    hook[1](p)
         if side_used:
             ev = torch.cuda.Event()
             ev.record(self._side)
@@ -339,15 +406,32 @@ class Adam(_Fused):
                 denom = state["exp_avg_sq"].sqrt() / ((1.0 - b2 ** t) ** 0.5) + group["eps"]
                 p.addcdiv_(state["exp_avg"], denom, value=-group["lr"] / (1.0 - b1 ** t))
 
-    def _entry(self, group, p, g, shadow):
+    def _next_step(self, p):
+        """the parameter's state, created at its first step, with ``step`` counted up -> (state, step)"""
         state = self.state[p]
         if len(state) == 0:
             state["step"] = torch.tensor(0.0, dtype=torch.float32)
             state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
         state["step"] += 1
-        return int(state["step"].item()), AdamTensor(p.data_ptr(), g.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(),
-                                                     shadow.data_ptr() if shadow is not None else None, p.numel())
+        return state, int(state["step"].item())
+
+    def _entry(self, group, p, g, shadow):
+        state, step = self._next_step(p)
+        return step, AdamTensor(p.data_ptr(), g.data_ptr(), state["exp_avg"].data_ptr(), state["exp_avg_sq"].data_ptr(),
+                                shadow.data_ptr() if shadow is not None else None, p.numel())
+
+    def _factored_state(self, group, p):
+        return self._next_step(p)
+
+    def _launch_factored(self, group, p, rec, shadow, fstate, norm, skip, side):
+        state, step = fstate
+        b1, b2 = group["betas"]
+        d = rec.desc(p)
+        check(lib().yolo_adam_step_factored(ctypes.byref(d), ptr(p), ptr(state["exp_avg"]), ptr(state["exp_avg_sq"]), ptr(shadow), float(group["lr"]), float(b1),
+                                            float(b2), float(group["eps"]), float(group["weight_decay"]), step, ptr(norm), float(self.max_grad_norm or 0.0),
+                                            ptr(skip), BG_CUS if side is not None else 0,
+                                            ctypes.c_void_p(side.cuda_stream) if side is not None else stream()), "yolo_adam_step_factored")
 
     def _launch(self, group, step, tab, count, norm, skip, side):
         b1, b2 = group["betas"]
@@ -413,7 +497,8 @@ class SGD(_Fused):
                     g = g.add(buf, alpha=momentum) if group["nesterov"] else buf
                 p.add_(g, alpha=-group["lr"])
 
-    def _entry(self, group, p, g, shadow):
+    def _buffer(self, group, p):
+        """(momentum buffer or None, is this the parameter's first step?)"""
         buf, first = None, False
         if group["momentum"] != 0:
             state = self.state[p]
@@ -423,6 +508,21 @@ class SGD(_Fused):
                 buf = state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
             elif not (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()):
                 raise RuntimeError("yolo.optim.SGD needs contiguous fp32 momentum buffers on the device")
+        return buf, first
+
+    def _factored_state(self, group, p):
+        return self._buffer(group, p)
+
+    def _launch_factored(self, group, p, rec, shadow, fstate, norm, skip, side):
+        buf, first = fstate
+        d = rec.desc(p)
+        check(lib().yolo_sgd_step_factored(ctypes.byref(d), ptr(p), ptr(buf), ptr(shadow), float(group["lr"]), float(group["momentum"]), float(group["dampening"]),
+                                           float(group["weight_decay"]), int(bool(group["nesterov"])), int(first), ptr(norm), float(self.max_grad_norm or 0.0),
+                                           ptr(skip), BG_CUS if side is not None else 0,
+                                           ctypes.c_void_p(side.cuda_stream) if side is not None else stream()), "yolo_sgd_step_factored")
+
+    def _entry(self, group, p, g, shadow):
+        buf, first = self._buffer(group, p)
         return first, SgdTensor(p.data_ptr(), g.data_ptr(), buf.data_ptr() if buf is not None else None,
                                 shadow.data_ptr() if shadow is not None else None, p.numel())
 
@@ -476,6 +576,13 @@ class LARS(_Fused):
         super().__init__(params, dict(lr=lr, momentum=momentum, weight_decay=weight_decay, eta=eta, eps=eps, adapt=True), max_grad_norm)
         self._norms = None                        # this step's norms buffer
         self._norm_index: dict[int, int] = {}     # id(param) -> its tensor index in it
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        if CFG.FC_FACTORED or any(_plan_factored(pl) for pl in self.plans) or \
+                any(p.grad is None and fc_factors_of(p)[0] is not None for g in self.param_groups for p in g["params"]):
+            raise RuntimeError(FC_FACTORED_REFUSED.format(what="yolo.optim.LARS (its trust ratio needs the per-tensor norm of the gradient)"))
+        return super().step(closure)
 
     def _step_on_cpu(self, all_params):
         """CPU parameters: the same step in stock torch ops -- per-tensor sums of squares in double, the clip coefficient formed in fp32 as the
@@ -811,6 +918,9 @@ class GradAccumulator:
         self._have: set = set()              # ids whose accumulator holds something in this group
         if self.steps == 1:
             return
+        if CFG.FC_FACTORED or any(_plan_factored(r.plan) for r in self._overlapped):
+            raise RuntimeError(FC_FACTORED_REFUSED.format(what=f"yolo.optim.GradAccumulator(steps={self.steps}) (the sum of K factored gradients is "
+                                                               "not a product of two factors of one micro-batch)"))
         params = [p for p in model.parameters() if p.requires_grad]
         plans = {id(r.plan): (r.plan, r) for r in self._overlapped}
         on_gpu = bool(params) and params[0].is_cuda
@@ -825,6 +935,8 @@ class GradAccumulator:
                 plans.setdefault(id(plan), (plan, None))
         covered = set()
         for plan, red in plans.values():
+            if _plan_factored(plan):
+                raise RuntimeError(FC_FACTORED_REFUSED.format(what=f"yolo.optim.GradAccumulator(steps={self.steps})"))
             self._arenas.append((plan, torch.empty_like(plan.arena), red is not None))
             covered |= {id(p) for p in plan.params}
             if red is not None:
