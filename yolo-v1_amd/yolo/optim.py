@@ -87,7 +87,7 @@ def grad_norm_sq(params, known=None) -> torch.Tensor:
                 slots = ctypes.c_long(0)
                 check(lib().yolo_sumsq_fixed_slots(gn, len(grads), ctypes.byref(slots)), "yolo_sumsq_fixed_slots")
                 st = stream()
-                scratch = _norm_scratch(dev, st, slots.value)
+                scratch = _scratch("sumsq", dev, st, slots.value)
                 check(lib().yolo_sumsq_f32_multi_fixed(gp, gn, len(grads), ptr(scratch), scratch.numel(), ptr(acc), st), "yolo_sumsq_f32_multi_fixed")
             else:
                 check(lib().yolo_sumsq_f32_multi(gp, gn, len(grads), ptr(acc), stream()), "yolo_sumsq_f32_multi")
@@ -96,17 +96,18 @@ def grad_norm_sq(params, known=None) -> torch.Tensor:
     return acc
 
 
-_NORM_SCRATCH: dict = {}
+_SCRATCH: dict = {}
 
 
-def _norm_scratch(dev, st, slots: int) -> torch.Tensor:
-    """fp64 scratch of the order-fixed norm, one per device and stream (launches of one stream use it one after the other), grown on demand"""
-    key = (dev.index, st.value or 0)
-    buf = _NORM_SCRATCH.get(key)
-    if buf is None or buf.numel() < slots:
+def _scratch(what: str, dev, st, numel: int) -> torch.Tensor:
+    """fp64 scratch ``what`` ("sumsq": the slots of the order-fixed norms; "lars": the 2 x count doubles yolo_lars_norms_multi stores), one per
+    device and stream (launches of one stream use it one after the other), grown on demand"""
+    key = (what, dev.index, st.value or 0)
+    buf = _SCRATCH.get(key)
+    if buf is None or buf.numel() < numel:
         if buf is not None:
             buf.record_stream(torch.cuda.current_stream(dev))
-        buf = _NORM_SCRATCH[key] = torch.empty(max(slots, 1), dtype=torch.float64, device=dev)
+        buf = _SCRATCH[key] = torch.empty(max(numel, 1), dtype=torch.float64, device=dev)
     return buf
 
 
@@ -141,7 +142,7 @@ def fc_factored_sumsq(weight, rec, acc: torch.Tensor) -> None:
     need = ctypes.c_long(0)
     check(lib().yolo_fc_factored_sumsq_slots(ctypes.byref(d), ctypes.byref(need)), "yolo_fc_factored_sumsq_slots")
     st = stream()
-    scratch = _norm_scratch(acc.device, st, need.value)
+    scratch = _scratch("sumsq", acc.device, st, need.value)
     check(lib().yolo_fc_factored_sumsq(ctypes.byref(d), ptr(scratch), scratch.numel(), ptr(acc), st), "yolo_fc_factored_sumsq")
 
 
@@ -208,6 +209,60 @@ class _Fused(torch.optim.Optimizer):
             known.update(plan.grad_norm_sq)
             plan.grad_norm_sq.clear()
         return known
+
+    def _begin_cpu_step(self, all_params, norm_sq=None):
+        """the head of every ``_step_on_cpu``: drains the plans' norm hints, forms the global gradient norm (from ``norm_sq`` where the caller
+        has the squared one already, else from the gradients and the hints) and consumes ``skip_if`` into ``last_skip``
+        -> (the norm as a double tensor, None without ``max_grad_norm``; does the flag cancel the step?)"""
+        known = self._known_norms()
+        total = None
+        if self.max_grad_norm is not None:
+            total = (grad_norm_sq(all_params, known) if norm_sq is None else norm_sq).sqrt()
+        skip, self.skip_if = self.skip_if, None
+        self.last_skip = skip
+        return total, skip is not None and float(skip) != 0.0
+
+    def _sgd_step_on_cpu(self, total, trust=None):
+        """SGD with momentum in stock torch ops, for SGD and LARS: the clip coefficient formed in fp32 as the kernels form it (clip_coefficient in
+        csrc/multi_tensor.h, which is clip_grad_norm_'s), then torch.optim.SGD's own sequence of operations.  ``trust(group, p, g, clip)``: LARS's
+        scaling of the clipped, regularised gradient ``g``"""
+        clip = None
+        if total is not None:
+            clip = (torch.tensor(self.max_grad_norm, dtype=torch.float32) / (total.float() + torch.tensor(1e-6, dtype=torch.float32))).clamp(max=1.0)
+        for group in self.param_groups:
+            momentum, wd = group["momentum"], group["weight_decay"]
+            for p in group["params"]:
+                if p.grad is None:
+                    continue
+                g = p.grad.float()
+                if clip is not None:
+                    g = g * clip
+                if wd != 0:
+                    g = g.add(p, alpha=wd)
+                if trust is not None:
+                    g = trust(group, p, g, clip)
+                if momentum != 0:
+                    state = self.state[p]
+                    buf = state.get("momentum_buffer")
+                    if buf is None:
+                        buf = state["momentum_buffer"] = g.clone()
+                    else:
+                        buf.mul_(momentum).add_(g, alpha=1 - group.get("dampening", 0))
+                    g = g.add(buf, alpha=momentum) if group.get("nesterov", False) else buf
+                p.add_(g, alpha=-group["lr"])
+
+    def _momentum_buffer(self, group, p):
+        """(momentum buffer or None, is this the parameter's first step?)"""
+        buf, first = None, False
+        if group["momentum"] != 0:
+            state = self.state[p]
+            buf = state.get("momentum_buffer")
+            first = buf is None
+            if first:
+                buf = state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            elif not (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()):
+                raise RuntimeError(f"yolo.optim.{type(self).__name__} needs contiguous fp32 momentum buffers on the device")
+        return buf, first
 
     def _clip_norm_sq(self, all_params):
         """device double with the global squared gradient norm the step launches clip by (None: no clipping), enqueued on the current stream in
@@ -379,27 +434,16 @@ class Adam(_Fused):
         """CPU parameters (the reference's ``--device cpu`` runs, the gloo tests of the data-parallel path): the same step in stock
         torch ops -- clip coefficient min(1, max_norm / (|g| + 1e-6)) from the squared norms (incl. the plans' hints), then the
         arithmetic of adam1 in optim.hip, which is torch.optim.Adam's."""
-        known = self._known_norms()
-        clip = 1.0
-        if self.max_grad_norm is not None:
-            total = float(grad_norm_sq(all_params, known).sqrt())
-            clip = min(1.0, self.max_grad_norm / (total + 1e-6))
-        skip, self.skip_if = self.skip_if, None
-        self.last_skip = skip
-        if skip is not None and float(skip) != 0.0:
+        total, skipped = self._begin_cpu_step(all_params)
+        if skipped:
             return
+        clip = 1.0 if total is None else min(1.0, self.max_grad_norm / (float(total) + 1e-6))
         for group in self.param_groups:
             b1, b2 = group["betas"]
             for p in group["params"]:
                 if p.grad is None:
                     continue
-                state = self.state[p]
-                if len(state) == 0:
-                    state["step"] = torch.tensor(0.0, dtype=torch.float32)
-                    state["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                    state["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                state["step"] += 1
-                t = int(state["step"].item())
+                state, t = self._next_step(p)
                 g = p.grad.float() * clip + group["weight_decay"] * p
                 state["exp_avg"].lerp_(g, 1.0 - b1)
                 state["exp_avg_sq"].mul_(b2).addcmul_(g, g, value=1.0 - b2)
@@ -466,52 +510,13 @@ class SGD(_Fused):
                                       maximize=False, foreach=None, differentiable=False, fused=None), max_grad_norm)
 
     def _step_on_cpu(self, all_params):
-        """CPU parameters: the same step in stock torch ops -- the clip coefficient formed in fp32 as the kernels form it
-        (clip_coefficient in csrc/multi_tensor.h, which is clip_grad_norm_'s), then torch.optim.SGD's own sequence of operations."""
-        known = self._known_norms()
-        clip = None
-        if self.max_grad_norm is not None:
-            total = grad_norm_sq(all_params, known).sqrt().float()
-            clip = (torch.tensor(self.max_grad_norm, dtype=torch.float32) / (total + torch.tensor(1e-6, dtype=torch.float32))).clamp(max=1.0)
-        skip, self.skip_if = self.skip_if, None
-        self.last_skip = skip
-        if skip is not None and float(skip) != 0.0:
-            return
-        for group in self.param_groups:
-            momentum, wd = group["momentum"], group["weight_decay"]
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                g = p.grad.float()
-                if clip is not None:
-                    g = g * clip
-                if wd != 0:
-                    g = g.add(p, alpha=wd)
-                if momentum != 0:
-                    state = self.state[p]
-                    buf = state.get("momentum_buffer")
-                    if buf is None:
-                        buf = state["momentum_buffer"] = g.clone()
-                    else:
-                        buf.mul_(momentum).add_(g, alpha=1 - group["dampening"])
-                    g = g.add(buf, alpha=momentum) if group["nesterov"] else buf
-                p.add_(g, alpha=-group["lr"])
-
-    def _buffer(self, group, p):
-        """(momentum buffer or None, is this the parameter's first step?)"""
-        buf, first = None, False
-        if group["momentum"] != 0:
-            state = self.state[p]
-            buf = state.get("momentum_buffer")
-            first = buf is None
-            if first:
-                buf = state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            elif not (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()):
-                raise RuntimeError("yolo.optim.SGD needs contiguous fp32 momentum buffers on the device")
-        return buf, first
+        """CPU parameters: the same step in stock torch ops (``_Fused._sgd_step_on_cpu``)"""
+        total, skipped = self._begin_cpu_step(all_params)
+        if not skipped:
+            self._sgd_step_on_cpu(total)
 
     def _factored_state(self, group, p):
-        return self._buffer(group, p)
+        return self._momentum_buffer(group, p)
 
     def _launch_factored(self, group, p, rec, shadow, fstate, norm, skip, side):
         buf, first = fstate
@@ -522,7 +527,7 @@ class SGD(_Fused):
                                            ctypes.c_void_p(side.cuda_stream) if side is not None else stream()), "yolo_sgd_step_factored")
 
     def _entry(self, group, p, g, shadow):
-        buf, first = self._buffer(group, p)
+        buf, first = self._momentum_buffer(group, p)
         return first, SgdTensor(p.data_ptr(), g.data_ptr(), buf.data_ptr() if buf is not None else None,
                                 shadow.data_ptr() if shadow is not None else None, p.numel())
 
@@ -533,20 +538,6 @@ class SGD(_Fused):
             check(lib().yolo_sgd_step_multi_bg(tab, count, *h, BG_CUS, ctypes.c_void_p(side.cuda_stream)), "yolo_sgd_step_multi_bg")
         else:
             check(lib().yolo_sgd_step_multi(tab, count, *h, stream()), "yolo_sgd_step_multi")
-
-
-_LARS_NORMS: dict = {}
-
-
-def _lars_norms(dev, st, count: int) -> torch.Tensor:
-    """the 2 x count doubles yolo_lars_norms_multi stores, one buffer per device and stream like the scratch beside it, grown on demand"""
-    key = (dev.index, st.value or 0)
-    buf = _LARS_NORMS.get(key)
-    if buf is None or buf.numel() < 2 * count:
-        if buf is not None:
-            buf.record_stream(torch.cuda.current_stream(dev))
-        buf = _LARS_NORMS[key] = torch.empty(max(2 * count, 2), dtype=torch.float64, device=dev)
-    return buf
 
 
 class LARS(_Fused):
@@ -586,44 +577,25 @@ class LARS(_Fused):
 
     def _step_on_cpu(self, all_params):
         """CPU parameters: the same step in stock torch ops -- per-tensor sums of squares in double, the clip coefficient formed in fp32 as the
-        kernels form it, the trust ratio in double narrowed to fp32, then SGD.  With ``adapt=False`` it is yolo.optim.SGD's CPU step."""
-        self._known_norms()
+        kernels form it, the trust ratio in double narrowed to fp32, then SGD (``_Fused._sgd_step_on_cpu``: with ``adapt=False`` it is
+        yolo.optim.SGD's CPU step).  The plans' hints are drained unused."""
         sums = {id(p): (p.detach().double().pow(2).sum(), p.grad.double().pow(2).sum()) for p in all_params}
-        clip = None
-        if self.max_grad_norm is not None:
-            acc = torch.zeros((), dtype=torch.float64)
-            for p in all_params:
-                acc += sums[id(p)][1]
-            clip = (torch.tensor(self.max_grad_norm, dtype=torch.float32) / (acc.sqrt().float() + torch.tensor(1e-6, dtype=torch.float32))).clamp(max=1.0)
-        skip, self.skip_if = self.skip_if, None
-        self.last_skip = skip
-        if skip is not None and float(skip) != 0.0:
+        acc = torch.zeros((), dtype=torch.float64)
+        for p in all_params:
+            acc += sums[id(p)][1]
+        total, skipped = self._begin_cpu_step(all_params, acc)
+        if skipped:
             return
         f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
-        for group in self.param_groups:
-            momentum, wd = group["momentum"], group["weight_decay"]
-            for p in group["params"]:
-                if p.grad is None:
-                    continue
-                g = p.grad.float()
-                if clip is not None:
-                    g = g * clip
-                if wd != 0:
-                    g = g.add(p, alpha=wd)
-                if group.get("adapt", True):
-                    wn = float(sums[id(p)][0].sqrt())
-                    gn = (float(clip) if clip is not None else 1.0) * float(sums[id(p)][1].sqrt())
-                    if wn > 0.0 and gn > 0.0:
-                        g = g * torch.tensor(f32(group["eta"]) * wn / (gn + f32(wd) * wn + f32(group["eps"])), dtype=torch.float32)
-                if momentum != 0:
-                    state = self.state[p]
-                    buf = state.get("momentum_buffer")
-                    if buf is None:
-                        buf = state["momentum_buffer"] = g.clone()
-                    else:
-                        buf.mul_(momentum).add_(g)
-                    g = buf
-                p.add_(g, alpha=-group["lr"])
+
+        def trust(group, p, g, clip):
+            if group.get("adapt", True):
+                wn = float(sums[id(p)][0].sqrt())
+                gn = (float(clip) if clip is not None else 1.0) * float(sums[id(p)][1].sqrt())
+                if wn > 0.0 and gn > 0.0:
+                    g = g * torch.tensor(f32(group["eta"]) * wn / (gn + f32(group["weight_decay"]) * wn + f32(group["eps"])), dtype=torch.float32)
+            return g
+        self._sgd_step_on_cpu(total, trust)
 
     def _clip_norm_sq(self, all_params):
         """one norms call for all parameters with gradients, in the foreground; -> its g_total (None without max_grad_norm)"""
@@ -644,23 +616,15 @@ class LARS(_Fused):
         gn = (ctypes.c_long * count)(*[p.numel() for p in all_params])
         slots = ctypes.c_long(0)
         check(lib().yolo_lars_norm_slots(gn, count, ctypes.byref(slots)), "yolo_lars_norm_slots")
-        scratch = _norm_scratch(dev, st, slots.value)
-        self._norms = _lars_norms(dev, st, count)
+        scratch = _scratch("sumsq", dev, st, slots.value)
+        self._norms = _scratch("lars", dev, st, 2 * count)
         self._norm_index = {id(p): i for i, p in enumerate(all_params)}
         total = torch.empty((), dtype=torch.float64, device=dev) if self.max_grad_norm is not None else None
         check(lib().yolo_lars_norms_multi(pp, gp, gn, count, ptr(scratch), scratch.numel(), ptr(self._norms), ptr(total), st), "yolo_lars_norms_multi")
         return total
 
     def _entry(self, group, p, g, shadow):
-        buf, first = None, False
-        if group["momentum"] != 0:
-            state = self.state[p]
-            buf = state.get("momentum_buffer")
-            first = buf is None
-            if first:
-                buf = state["momentum_buffer"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-            elif not (buf.is_cuda and buf.dtype == torch.float32 and buf.is_contiguous()):
-                raise RuntimeError("yolo.optim.LARS needs contiguous fp32 momentum buffers on the device")
+        buf, first = self._momentum_buffer(group, p)
         adapt = bool(group.get("adapt", True))
         norms = self._norms.data_ptr() + 16 * self._norm_index[id(p)] if adapt else None
         return first, _hip.LarsTensor(p.data_ptr(), g.data_ptr(), buf.data_ptr() if buf is not None else None,
