@@ -65,6 +65,18 @@ int yolo_stream_create(int low, yolo_stream_t *out);
 int yolo_decode(const float *pred, int N, int S, int B, int C, double conf_thr,
                 double *rec, int32_t *counts, yolo_stream_t stream);
 
+/* Class-specific scores (YOLOv1 paper section 2; Darknet get_detection_boxes): every box b of every cell is a candidate
+ * of EVERY class c with score (double)conf_b * (double)prob_c, kept iff score > conf_thr.  One launch, one workgroup per
+ * (image, class).
+ *   pred    [N][S][S][5B+C] fp32
+ *   rec     [N][C][S*S*B][6] f64 = {c, score, x, y, w, h} (x, y, w, h as yolo_decode); of group (n, c) the first
+ *           counts[n][c] rows are valid, in (row i, col j, box b) scan order; the rows behind them are not written
+ *   counts  [N][C] int32
+ * rec viewed as N*C images of S*S*B records is what yolo_nms and yolo_map_match take (all records of a group share one class).
+ * Limits: S*S*B <= 1024, B <= 8 (those of yolo_decode).  YOLO_E_ARG on a null pointer, N < 0 or C < 1; N == 0 succeeds. */
+int yolo_decode_classes(const float *pred, int N, int S, int B, int C, double conf_thr,
+                        double *rec /*[N][C][S*S*B][6]*/, int32_t *counts /*[N][C]*/, yolo_stream_t stream);
+
 /* Replaces mAPMetric._parse_ground_truth (src/yolo/metrics.py:232-256).
  *   rec [N][S*S][5] f64 = {class_id, x, y, w, h}; counts [N]. */
 int yolo_decode_gt(const float *tgt, int N, int S, int B, int C,

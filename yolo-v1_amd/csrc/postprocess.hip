@@ -7,6 +7,14 @@
 //   decode   src/yolo/inference.py:170-210, src/yolo/metrics.py:185-218, :232-256
 //   IoU      src/yolo/inference.py:229-249 + src/yolo/schemas.py:18-55 ; src/yolo/metrics.py:313-341
 //   NMS      src/yolo/inference.py:298-317 ; src/yolo/metrics.py:270-296
+//
+// Class-specific scoring (yolo_decode_classes; YOLOv1 paper section 2, Darknet get_detection_boxes + do_nms_sort) is
+// not in the reference: every box is a candidate of EVERY class with score conf_b * prob_c.  Shape of its launch: one
+// workgroup per (image, class), not one per image that walks the classes.  A batch of 16 then fills 320 workgroups
+// instead of 16 on 256 compute units, a group's compaction chain (three barriers per round of 128 candidates) is not
+// repeated C times back to back, and the group's base address and class are plain workgroup constants.  The price is
+// that the 5B box floats of a cell are read once per class, from L2 -- 12 KB per image at S = 7.  The record table is
+// [N][C][S*S*B][6], so (image, class) groups are the "images" yolo_nms and yolo_map_match already take.
 #include "common.h"
 
 namespace yolo {
@@ -70,6 +78,54 @@ __global__ void __launch_bounds__(128) decode_kernel(const float *__restrict__ p
         __syncthreads();
     }
     if (threadIdx.x == 0) counts[img] = base_s;
+}
+
+// class-specific scores: workgroup g = (image, class), the candidates of that class in (i, j, b) scan order; the same
+// compaction as decode_kernel.  Rows behind counts[g] are not written.
+__global__ void __launch_bounds__(128) decode_classes_kernel(const float *__restrict__ pred, int S, int B, int C, double thr,
+                                                             double *__restrict__ rec, int *__restrict__ counts)
+{
+    const int D = B * 5 + C;
+    const int ncand = S * S * B;
+    const int img = blockIdx.x / C, cls = blockIdx.x - img * C;
+    const float *p = pred + (size_t)img * S * S * D;
+    double *out = rec + (size_t)blockIdx.x * ncand * 6;
+    __shared__ int wave_cnt[2];
+    __shared__ int base_s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) base_s = 0;
+    __syncthreads();
+    for (int t0 = 0; t0 < ncand; t0 += 128) {
+        const int t = t0 + threadIdx.x;
+        bool keep = false;
+        double r1 = 0, r2 = 0, r3 = 0, r4 = 0, r5 = 0;
+        if (t < ncand) {
+            const int cell = t / B, b = t - cell * B;
+            const int i = cell / S, j = cell - i * S;
+            const float *c = p + (size_t)cell * D;
+            const float *bx = c + b * 5;
+            const double prob = (double)c[B * 5 + cls];
+            r2 = ((double)j + (double)bx[0]) / (double)S;
+            r3 = ((double)i + (double)bx[1]) / (double)S;
+            r4 = (double)bx[2];
+            r5 = (double)bx[3];
+            r1 = (double)bx[4] * prob;
+            keep = r1 > thr;
+        }
+        const unsigned long long m = __ballot(keep);
+        const int below = __popcll(m & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_cnt[wave] = __popcll(m);
+        __syncthreads();
+        const int base = base_s + (wave == 1 ? wave_cnt[0] : 0);
+        if (keep) {
+            double *r = out + (size_t)(base + below) * 6;
+            r[0] = (double)cls; r[1] = r1; r[2] = r2; r[3] = r3; r[4] = r4; r[5] = r5;
+        }
+        __syncthreads();
+        if (threadIdx.x == 0) base_s += wave_cnt[0] + wave_cnt[1];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) counts[blockIdx.x] = base_s;
 }
 
 __global__ void __launch_bounds__(128) decode_gt_kernel(const float *__restrict__ tgt, int S, int B, int C,
@@ -427,6 +483,16 @@ YOLO_API int yolo_decode(const float *pred, int N, int S, int B, int C, double c
     if (N == 0) return 0;
     hipLaunchKernelGGL(decode_kernel, dim3(N), dim3(128), 0, STRM(stream), pred, S, B, C, conf_thr, rec, counts);
     return check_launch("yolo_decode");
+}
+
+YOLO_API int yolo_decode_classes(const float *pred, int N, int S, int B, int C, double conf_thr, double *rec, int32_t *counts, yolo_stream_t stream)
+{
+    if (!pred || !rec || !counts || N < 0 || S <= 0 || B <= 0 || C < 1) return fail(YOLO_E_ARG, "yolo_decode_classes: bad argument");
+    if (S * S * B > 1024 || B > 8) return fail(YOLO_E_UNSUPPORTED, "yolo_decode_classes: S*S*B=%d > 1024 or B=%d > 8", S * S * B, B);
+    if ((long)N * C > 0x7fffffffL) return fail(YOLO_E_UNSUPPORTED, "yolo_decode_classes: N*C=%ld groups exceed one grid", (long)N * C);
+    if (N == 0) return 0;
+    hipLaunchKernelGGL(decode_classes_kernel, dim3(N * C), dim3(128), 0, STRM(stream), pred, S, B, C, conf_thr, rec, counts);
+    return check_launch("yolo_decode_classes");
 }
 
 YOLO_API int yolo_decode_gt(const float *tgt, int N, int S, int B, int C, double *rec, int32_t *counts, yolo_stream_t stream)

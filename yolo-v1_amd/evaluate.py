@@ -28,6 +28,9 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0)
     ap.add_argument("--output", default="evaluation_results.txt")
     ap.add_argument("--use-ema", action="store_true", help="evaluate the averaged weights of a train.py --ema-decay checkpoint (ema_state_dict)")
+    ap.add_argument("--scoring", choices=["argmax", "all"], default="argmax",
+                    help="argmax: one class per cell, the reference's protocol; all: every box scored for every class and NMS per class, "
+                         "the paper's / Darknet's test-time protocol")
     ap.add_argument("--batch-norm", action="store_true",
                     help="--backbone yolov1 without a checkpoint: the BatchNorm variant (a checkpoint's own batch_norm record decides otherwise)")
     a = ap.parse_args()
@@ -45,8 +48,11 @@ def main():
     elif a.use_ema:
         ap.error("--use-ema needs --checkpoint")
     model = model.to(a.device)
-    res = evaluate_model(model, loader, a.device, num_classes=20, conf_threshold=a.conf_threshold, nms_threshold=a.nms_threshold)
+    res = evaluate_model(model, loader, a.device, num_classes=20, conf_threshold=a.conf_threshold, nms_threshold=a.nms_threshold,
+                         scoring=a.scoring)
     lines = [f"{k}: {float(v):.6f}" for k, v in res.items()]
+    if a.scoring != "argmax":
+        lines.append(f"scoring: {a.scoring}")
     print("\n".join(lines[:12]))
     with open(a.output, "w") as f:
         f.write("\n".join(lines) + "\n")

@@ -47,12 +47,15 @@ def main():
     ap.add_argument("--nms-threshold", type=float, default=0.4)
     ap.add_argument("--output-dir", default=None)
     ap.add_argument("--use-ema", action="store_true", help="load the averaged weights of a train.py --ema-decay checkpoint (ema_state_dict)")
+    ap.add_argument("--scoring", choices=["argmax", "all"], default="argmax",
+                    help="argmax: one class per cell, the reference's protocol; all: every box scored for every class and NMS per class, "
+                         "the paper's / Darknet's test-time protocol")
     ap.add_argument("--batch-norm", action="store_true",
                     help="--backbone yolov1 without a checkpoint: the BatchNorm variant (a checkpoint's own batch_norm record decides otherwise)")
     a = ap.parse_args()
     engine = YOLOInference(load_model(a.checkpoint, a.device, backbone=a.backbone, use_ema=a.use_ema, batch_norm=a.batch_norm), device=a.device)
     for path in a.images:
-        dets = engine.predict(path, conf_threshold=a.conf_threshold, nms_threshold=a.nms_threshold, class_names=VOC_CLASSES)
+        dets = engine.predict(path, conf_threshold=a.conf_threshold, nms_threshold=a.nms_threshold, class_names=VOC_CLASSES, scoring=a.scoring)
         print(f"{path}: {len(dets)} detections")
         for d in dets:
             print(f"  {d.class_name:12s} {d.confidence:.3f} {d.bbox}")

@@ -88,3 +88,52 @@ def nms(rec: np.ndarray, thr: float, variant: int) -> np.ndarray:
             first.setdefault(c, pos)
         kept = kept[np.argsort([first[cls[k]] for k in kept], kind="stable")]
     return order[kept].astype(np.int32)
+
+
+# ------------------------------------------------------------------------------------------------
+# class-specific scoring (YOLOv1 paper section 2; Darknet get_detection_boxes + do_nms_sort): every box is a candidate of
+# every class with score conf_b * prob_c; each class is thresholded and NMS-filtered on its own
+# ------------------------------------------------------------------------------------------------
+SCORINGS = ("argmax", "all")
+
+
+def check_scoring(scoring: str) -> str:
+    if scoring not in SCORINGS:
+        raise ValueError(f"scoring must be one of {SCORINGS}, got {scoring!r}")
+    return scoring
+
+
+def decode_classes(pred: np.ndarray, conf_thr: float, S: int, B: int) -> list:
+    """(S,S,5B+C) fp32 -> C arrays (n_c,6) float64 of rows [c, conf_b*prob_c, x, y, w, h], each in (i,j,b) scan order."""
+    p = np.asarray(pred, dtype=np.float32).reshape(S, S, -1)
+    C = p.shape[-1] - B * 5
+    probs = p[..., B * 5:].astype(np.float64)                     # (S,S,C)
+    boxes = p[..., : B * 5].reshape(S, S, B, 5).astype(np.float64)
+    jj, ii = np.meshgrid(np.arange(S, dtype=np.float64), np.arange(S, dtype=np.float64))
+    rec = np.empty((S, S, B, 6), np.float64)
+    rec[..., 2] = (jj[..., None] + boxes[..., 0]) / S
+    rec[..., 3] = (ii[..., None] + boxes[..., 1]) / S
+    rec[..., 4] = boxes[..., 2]
+    rec[..., 5] = boxes[..., 3]
+    out = []
+    for c in range(C):
+        rec[..., 0] = c
+        rec[..., 1] = boxes[..., 4] * probs[..., c, None]
+        r = rec.reshape(-1, 6)
+        out.append(r[r[:, 1] > conf_thr])                          # boolean indexing copies
+    return out
+
+
+def nms_classes(groups: list, thr: float, variant: int):
+    """Per-class NMS over the lists of ``decode_classes`` -> (rec, keep) of one image: ``rec`` is the groups one behind the
+    other (class ascending, scan order), ``keep`` indexes it in the result order.  METRICS: classes ascending, inside a
+    class the NMS output (confidence) order.  INFERENCE: all kept detections by confidence descending, stable over that."""
+    rec = np.concatenate(groups) if len(groups) else np.zeros((0, 6))
+    keep, off = [], 0
+    for g in groups:
+        keep.append(nms(g, thr, variant).astype(np.int64) + off)
+        off += len(g)
+    keep = np.concatenate(keep) if keep else np.zeros(0, np.int64)
+    if variant == INFERENCE:
+        keep = keep[np.argsort(-rec[keep, 1], kind="stable")]
+    return rec.reshape(-1, 6), keep.astype(np.int32)

@@ -76,7 +76,10 @@ class YOLOInference:
 
     # ------------------------------------------------------------------ pipeline
     def predict(self, image_path: str, conf_threshold: float = 0.5, nms_threshold: float = 0.4,
-                class_names: list[str] | None = None) -> list[Detection]:
+                class_names: list[str] | None = None, scoring: str = "argmax") -> list[Detection]:
+        """scoring="all": the paper's test-time protocol -- every box scored for every class, NMS per class, the kept detections
+        of all classes by confidence (a box may come out under several classes)."""
+        _post_cpu.check_scoring(scoring)
         image = self.load_image(image_path)
         x = self.preprocess_image(image)
         with torch.no_grad():
@@ -85,8 +88,13 @@ class YOLOInference:
             from . import ops
             S, B = self.model.S, self.model.B
             C = pred.shape[-1] - 5 * B
-            (rec, keep), = ops.postprocess_host(pred[:1], conf_threshold, nms_threshold, ops._hip.NMS_INFERENCE, S, B, C)
+            (rec, keep), = ops.postprocess_host(pred[:1], conf_threshold, nms_threshold, ops._hip.NMS_INFERENCE, S, B, C, scoring)
             dets = self._records_to_detections(rec, class_names)   # validates every decoded box like the reference
+            return [dets[k] for k in keep]
+        if scoring == "all":
+            groups = _post_cpu.decode_classes(pred[0].detach().numpy(), conf_threshold, self.model.S, self.model.B)
+            rec, keep = _post_cpu.nms_classes(groups, nms_threshold, _post_cpu.INFERENCE)
+            dets = self._records_to_detections(rec, class_names)
             return [dets[k] for k in keep]
         dets = self.parse_predictions(pred[0], conf_threshold, class_names)
         return self.non_max_suppression(dets, nms_threshold)
@@ -100,9 +108,20 @@ class YOLOInference:
                                  confidence=conf, bbox=BoundingBox(x=x, y=y, width=w, height=h)))
         return out
 
-    def parse_predictions(self, pred: torch.Tensor, conf_threshold: float, class_names: list[str] | None = None) -> list[Detection]:
-        """(S,S,5B+C) -> Detections with conf*prob > threshold, (row, col, box) scan order."""
+    def parse_predictions(self, pred: torch.Tensor, conf_threshold: float, class_names: list[str] | None = None,
+                          scoring: str = "argmax") -> list[Detection]:
+        """(S,S,5B+C) -> Detections with conf*prob > threshold, (row, col, box) scan order.
+        scoring="all": conf_b*prob_c of every class c, the lists of the classes one behind the other (classes ascending)."""
         S, B = self.model.S, self.model.B
+        if _post_cpu.check_scoring(scoring) == "all":
+            if pred.is_cuda:
+                from . import ops
+                rec, cnt = ops.decode_classes(pred.unsqueeze(0), conf_threshold, S, B, pred.shape[-1] - 5 * B)
+                rec, cnt = rec[0].cpu().numpy(), cnt[0].cpu().numpy()
+                rec = rec[np.arange(rec.shape[1])[None, :] < cnt[:, None]]
+            else:
+                rec = np.concatenate(_post_cpu.decode_classes(pred.detach().numpy(), conf_threshold, S, B))
+            return self._records_to_detections(rec, class_names)
         if pred.is_cuda:
             from . import ops
             rec, cnt = ops.decode(pred.unsqueeze(0), conf_threshold, S, B, pred.shape[-1] - 5 * B)

@@ -15,6 +15,10 @@ size buckets and the overall precision / recall) is also done there, per image, 
 only ever meets the ground truths of its own image, and an image's kept list is the global confidence order restricted
 to that image -- and ``compute`` reduces to sorts, cumulative sums and the 11-point interpolation in vectorised NumPy
 (same arithmetic, same floats as the host path, which remains for lists filled by hand or on the CPU).
+
+``scoring="all"`` replaces the reference's one-class-per-cell decode by the paper's test-time protocol: every box scored for
+every class, NMS per class (``yolo_decode_classes``; DESIGN.md, "Class-specific scores for every box").  The default,
+``"argmax"``, is the reference's behaviour.
 """
 
 from __future__ import annotations
@@ -47,8 +51,10 @@ class mAPMetric:
     """PASCAL-VOC style mAP at one or several IoU thresholds (default 0.50:0.05:0.95)."""
 
     def __init__(self, num_classes: int, iou_thresholds: List[float] = None, conf_threshold: float = 0.01,
-                 nms_threshold: float = 0.4, S: int = 7, B: int = 2):
+                 nms_threshold: float = 0.4, S: int = 7, B: int = 2, scoring: str = "argmax"):
         self.num_classes = num_classes
+        # "argmax": the reference's shortcut, one class per cell; "all": the paper's protocol, every box scored for every class
+        self.scoring = _post_cpu.check_scoring(scoring)
         if iou_thresholds is None:
             self.iou_thresholds = [0.5 + 0.05 * i for i in range(10)]
         elif isinstance(iou_thresholds, (int, float)):
@@ -73,6 +79,8 @@ class mAPMetric:
     # ------------------------------------------------------------------ accumulation
     def update(self, predictions: torch.Tensor, targets: torch.Tensor):
         """predictions, targets: (batch, S, S, 5B+C)."""
+        if self.scoring == "all":
+            return self._update_all_classes(predictions, targets)
         if predictions.is_cuda:
             from . import ops
             C = predictions.shape[-1] - 5 * self.B
@@ -101,6 +109,45 @@ class mAPMetric:
         for i in range(predictions.shape[0]):
             self.all_predictions.append(self._apply_nms(self._parse_predictions(predictions[i])))
             self.all_ground_truths.append(self._parse_ground_truth(targets[i]))
+
+    def _update_all_classes(self, predictions: torch.Tensor, targets: torch.Tensor):
+        """scoring="all": every (image, class) group is an image of its own for yolo_nms and yolo_map_match (the image's ground
+        truths repeated for its C groups: matching is per class and per image, and map_match_kernel lets a ground truth be taken
+        only by predictions of its class).  Per image the kept lists of the classes follow each other, classes ascending."""
+        if not predictions.is_cuda:
+            for i in range(predictions.shape[0]):
+                groups = _post_cpu.decode_classes(predictions[i].detach().numpy(), self.conf_threshold, self.S, self.B)
+                rec, keep = _post_cpu.nms_classes(groups, self.nms_threshold, _post_cpu.METRICS)
+                self.all_predictions.append(_records_to_preds(rec[keep]))
+                self.all_ground_truths.append(self._parse_ground_truth(targets[i]))
+            return
+        from . import ops
+        N, M = predictions.shape[0], self.S * self.S * self.B
+        C = predictions.shape[-1] - 5 * self.B
+        rec, counts = ops.decode_classes(predictions, self.conf_threshold, self.S, self.B, C)
+        rec_g = rec.view(N * C, M, 6)
+        keep, kc = ops.nms(rec_g, counts.view(N * C), self.nms_threshold, ops._hip.NMS_METRICS)
+        grec, gcnt = ops.decode_gt(targets.to(predictions.device), self.S, self.B, C)
+        tp = bucket = None
+        if N > 0 and len(self.iou_thresholds) <= 15 and M <= 128 and grec.shape[1] <= 64 and self._dev_images == len(self.all_predictions):
+            tp, bucket = ops.map_match(rec_g, keep, kc, grec.repeat_interleave(C, 0), gcnt.repeat_interleave(C), self.iou_thresholds, 0.5,
+                                       (32 / 448) ** 2, (96 / 448) ** 2)
+        rec_h, counts_h = rec.cpu().numpy(), counts.cpu().numpy()
+        keep_h, kc_h = keep.view(N, C, M).cpu().numpy(), kc.view(N, C).cpu().numpy()
+        grec, gcnt = grec.cpu().numpy(), gcnt.cpu().numpy()
+        tp_h = None if tp is None else tp.view(N, C, M).cpu().numpy().view(np.uint64)
+        per_img = ops.classes_to_images(rec_h, counts_h, keep_h, kc_h, ops._hip.NMS_METRICS, tp_h)
+        kept = [r[0][r[1]] for r in per_img]
+        for n, k in enumerate(kept):
+            self.all_predictions.append(_records_to_preds(k))
+            self.all_ground_truths.append(_records_to_gts(grec[n, : gcnt[n]]))
+        if tp is not None:
+            bucket_h = bucket.view(N, C, -1)[:, 0].cpu().numpy()          # the C copies of an image's ground truths get the same buckets
+            allk = np.concatenate(kept)
+            self._dev.append((allk[:, 0].astype(np.int64), allk[:, 1].copy(), np.concatenate([r[2] for r in per_img]),
+                              np.concatenate([grec[n, : gcnt[n], 0] for n in range(N)]).astype(np.int64),
+                              np.concatenate([bucket_h[n, : gcnt[n]] for n in range(N)])))
+            self._dev_images += N
 
     # ---- per-image helpers (same names/returns as the reference; used by its tests) -------------
     def _parse_predictions(self, pred: torch.Tensor) -> List[Pred]:
@@ -361,11 +408,11 @@ class mAPMetric:
 
 def evaluate_model(model: nn.Module, dataloader: DataLoader, device: str, num_classes: int = 20,
                    iou_thresholds: List[float] = None, conf_threshold: float = 0.01, nms_threshold: float = 0.4,
-                   S: int = 7, B: int = 2) -> Dict[str, float]:
+                   S: int = 7, B: int = 2, scoring: str = "argmax") -> Dict[str, float]:
     """Run ``model`` over ``dataloader`` and return the ``mAPMetric.compute()`` dictionary."""
     model.eval()
     metric = mAPMetric(num_classes=num_classes, iou_thresholds=iou_thresholds, conf_threshold=conf_threshold,
-                       nms_threshold=nms_threshold, S=S, B=B)
+                       nms_threshold=nms_threshold, S=S, B=B, scoring=scoring)
     try:
         from tqdm import tqdm
         batches = tqdm(dataloader, desc="Evaluating", unit="batch")

@@ -7,6 +7,7 @@ from __future__ import annotations
 
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _hip
@@ -31,6 +32,18 @@ def decode(pred: torch.Tensor, conf_thr: float, S: int, B: int, C: int):
     rec = torch.empty((N, S * S * B, 6), dtype=torch.float64, device=pred.device)
     counts = torch.empty((N,), dtype=torch.int32, device=pred.device)
     check(lib().yolo_decode(ptr(pred), N, S, B, C, float(conf_thr), ptr(rec), ptr(counts), stream()), "yolo_decode")
+    return rec, counts
+
+
+@_hip.device_guard
+def decode_classes(pred: torch.Tensor, conf_thr: float, S: int, B: int, C: int):
+    """(N,S,S,5B+C) fp32 -> rec (N,C,S*S*B,6) f64 {c,conf_b*prob_c,x,y,w,h}, counts (N,C) i32: every box scored for every
+    class (YOLOv1 paper section 2).  ``rec.view(N*C, S*S*B, 6)`` / ``counts.view(N*C)`` are what ``nms`` and ``map_match`` take."""
+    pred = _as_f32_dev(pred)
+    N = pred.shape[0]
+    rec = torch.empty((N, C, S * S * B, 6), dtype=torch.float64, device=pred.device)
+    counts = torch.empty((N, C), dtype=torch.int32, device=pred.device)
+    check(lib().yolo_decode_classes(ptr(pred), N, S, B, C, float(conf_thr), ptr(rec), ptr(counts), stream()), "yolo_decode_classes")
     return rec, counts
 
 
@@ -86,9 +99,39 @@ def map_match(rec: torch.Tensor, keep: torch.Tensor, kc: torch.Tensor, grec: tor
     return tp, bucket
 
 
-def postprocess_host(pred: torch.Tensor, conf_thr: float, nms_thr: float, variant: int, S: int, B: int, C: int):
+def classes_to_images(rec_h, counts_h, keep_h, kc_h, variant: int, extra=None):
+    """Host arrays of ``decode_classes`` + grouped ``nms`` -> per image (rec, keep) like ``_post_cpu.nms_classes``: the valid rows
+    of the image's C groups one behind the other, and the kept indices into them in the result order of ``variant``.
+    ``extra`` (N,C,M), e.g. the TP bits of ``map_match``: its kept entries in that order come third."""
+    N, C, M, _ = rec_h.shape
+    slot = np.arange(M)
+    out = []
+    for n in range(N):
+        valid = slot[None, :] < counts_h[n][:, None]                       # (C,M), row-major == class ascending, scan order
+        kvalid = slot[None, :] < kc_h[n][:, None]
+        off = np.concatenate(([0], np.cumsum(counts_h[n][:-1]))).astype(np.int64)
+        rec = rec_h[n][valid]
+        keep = (keep_h[n].astype(np.int64) + off[:, None])[kvalid]
+        ex = None if extra is None else extra[n][kvalid]
+        if variant == _hip.NMS_INFERENCE:
+            order = np.argsort(-rec[keep, 1], kind="stable")
+            keep = keep[order]
+            ex = None if ex is None else ex[order]
+        out.append((rec, keep.astype(np.int32)) if extra is None else (rec, keep.astype(np.int32), ex))
+    return out
+
+
+def postprocess_host(pred: torch.Tensor, conf_thr: float, nms_thr: float, variant: int, S: int, B: int, C: int, scoring: str = "argmax"):
     """decode + NMS on the device for a batch, ONE device->host copy.
-    Returns per image (rec[n] as a (cnt,6) float64 numpy array, kept indices int32 numpy array)."""
+    Returns per image (rec[n] as a (cnt,6) float64 numpy array, kept indices int32 numpy array).
+    scoring="all": class-specific scores, NMS per (image, class) group by the same ``yolo_nms``; rec[n] holds the image's
+    C groups one behind the other."""
+    from ._post_cpu import check_scoring
+    if check_scoring(scoring) == "all":
+        rec, counts = decode_classes(pred, conf_thr, S, B, C)
+        N = rec.shape[0]
+        keep, kc = nms(rec.view(N * C, S * S * B, 6), counts.view(N * C), nms_thr, variant)
+        return classes_to_images(rec.cpu().numpy(), counts.cpu().numpy(), keep.view(N, C, -1).cpu().numpy(), kc.view(N, C).cpu().numpy(), variant)
     rec, counts = decode(pred, conf_thr, S, B, C)
     keep, kc = nms(rec, counts, nms_thr, variant)
     rec_h, counts_h, keep_h, kc_h = rec.cpu().numpy(), counts.cpu().numpy(), keep.cpu().numpy(), kc.cpu().numpy()
