@@ -790,6 +790,31 @@ int yolo_map_match(const double *rec, const int32_t *keep, const int32_t *keep_c
                    int32_t *gt_bucket, yolo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * PASCAL VOC devkit matching ("VOC devkit evaluation"; not in the reference): the kept detections of
+ * yolo_decode / yolo_decode_classes + yolo_nms (metrics variant) against the ANNOTATED ground truth of their images, with
+ * `difficult` flags, on clamped pixel boxes with the devkit's + 1 overlap, and the compaction of the result, in one launch
+ * (one single-wave workgroup per group).
+ *   rec, keep, keep_counts   as yolo_nms takes and leaves them: n_groups groups of max_per_group records
+ *   groups_per_image         C behind yolo_decode_classes, 1 behind yolo_decode; group g belongs to image g / groups_per_image
+ *   gt_box [G][4] f64 pixel {xmin, ymin, xmax, ymax}, gt_cls [G], gt_difficult [G] (0 / 1), gt_off [images + 1]: image n owns
+ *   rows gt_off[n] .. gt_off[n+1] - 1; img_wh [images][2] f64 = {W, H} in pixels.  All in device memory.
+ *   max_gt                   the largest number of ground truths of one image of the batch (the caller knows its table)
+ *   thresholds               HOST array of T IoU thresholds
+ * A ground truth of another class than the detection's never takes part.  Output rows are dense: group order, inside a
+ * group NMS order; row r of a group starts at the sum of keep_counts of the groups in front of it, out_total[0] = number of
+ * rows, rows behind it are not written:
+ *   out_score [.] f64, out_cls_img [.][2] = {class, image_base + image}, out_box [.][4] = the clamped pixel corners,
+ *   out_status [.] : bits 2t, 2t+1 = 0 FP, 1 TP, 2 ignored (best match is difficult) at thresholds[t].
+ * The outputs hold n_groups * max_per_group rows at most.
+ * Limits (YOLO_E_ARG, like null pointers and negative sizes, before any launch): 1 <= T <= 16, max_gt <= 256,
+ * 1 <= max_per_group <= 1024, n_groups a multiple of groups_per_image.  n_groups == 0 succeeds with out_total[0] = 0. */
+int yolo_voc_match(const double *rec, const int32_t *keep, const int32_t *keep_counts, int n_groups, int max_per_group,
+                   int groups_per_image, const double *gt_box, const int32_t *gt_cls, const unsigned char *gt_difficult,
+                   const int32_t *gt_off, const double *img_wh, int max_gt, int image_base, const double *thresholds, int T,
+                   double *out_score, int32_t *out_cls_img, uint32_t *out_status, double *out_box, int32_t *out_total,
+                   yolo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Image preprocessing.  Replaces YOLOInference.transform / the eval transform of the reference
  * (src/yolo/inference.py:58-66, src/yolo/dataset.py:224-233): Resize((Ho,Wo)) = PIL.Image.resize(BILINEAR) ->
  * ToTensor (/255) -> Normalize(mean, std), from decoded uint8 RGB [N][Hs][Ws][3] in device memory.

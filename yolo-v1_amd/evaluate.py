@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """mAP evaluation of a checkpoint (the reference's src/evaluate.py surface; defaults batch 16,
-conf 0.01, nms 0.4 as in src/evaluate.py:18-95) with an additive --backbone / --synthetic flag."""
+conf 0.01, nms 0.4 as in src/evaluate.py:18-95) with an additive --backbone / --synthetic flag and, with --protocol voc,
+the PASCAL VOC devkit's evaluation (yolo/voc_eval.py) instead of the reference's."""
 
 from __future__ import annotations
 
@@ -33,8 +34,16 @@ def main():
                          "the paper's / Darknet's test-time protocol")
     ap.add_argument("--batch-norm", action="store_true",
                     help="--backbone yolov1 without a checkpoint: the BatchNorm variant (a checkpoint's own batch_norm record decides otherwise)")
+    ap.add_argument("--protocol", choices=["grid", "voc"], default="grid",
+                    help="grid: ground truth from the S x S target, the reference's matching; voc: the PASCAL VOC devkit's -- every annotated "
+                         "object, difficult flags, pixel overlaps (yolo/voc_eval.py)")
+    ap.add_argument("--ap-mode", choices=["voc07", "area"], default="voc07", help="--protocol voc: the 11-point AP of VOC2007 or the area of VOC2010+")
+    ap.add_argument("--iou-thresholds", default="0.5", help="--protocol voc: comma-separated IoU thresholds, the first is the one of mAP")
+    ap.add_argument("--write-detections", default=None, metavar="DIR", help="--protocol voc: write the devkit's comp4_det_test_<class>.txt files there")
     a = ap.parse_args()
-    ck = torch.load(a.checkpoint, map_location=a.device, weights_only=True) if a.checkpoint else None
+    if a.protocol != "voc" and (a.write_detections or a.ap_mode != "voc07" or a.iou_thresholds != "0.5"):
+        ap.error("--ap-mode, --iou-thresholds and --write-detections need --protocol voc")
+    ck =torch.load(a.checkpoint, map_location=a.device, weights_only=True) if a.checkpoint else None
     bn = bool(ck.get("batch_norm", False)) if ck is not None else a.batch_norm
     if bn and a.backbone != "yolov1":
         ap.error("batch_norm (the checkpoint's record, or --batch-norm) needs --backbone yolov1")
@@ -48,11 +57,19 @@ def main():
     elif a.use_ema:
         ap.error("--use-ema needs --checkpoint")
     model = model.to(a.device)
-    res = evaluate_model(model, loader, a.device, num_classes=20, conf_threshold=a.conf_threshold, nms_threshold=a.nms_threshold,
-                         scoring=a.scoring)
+    if a.protocol == "voc":
+        from yolo.voc_eval import evaluate_voc
+        res = evaluate_voc(model, ds, a.device, num_classes=20, iou_thresholds=[float(t) for t in a.iou_thresholds.split(",")], ap_mode=a.ap_mode,
+                           scoring=a.scoring, conf_threshold=a.conf_threshold, nms_threshold=a.nms_threshold, batch_size=a.batch_size,
+                           write_detections=a.write_detections)
+    else:
+        res = evaluate_model(model, loader, a.device, num_classes=20, conf_threshold=a.conf_threshold, nms_threshold=a.nms_threshold,
+                             scoring=a.scoring)
     lines = [f"{k}: {float(v):.6f}" for k, v in res.items()]
     if a.scoring != "argmax":
         lines.append(f"scoring: {a.scoring}")
+    if a.protocol == "voc":
+        lines += ["protocol: voc", f"ap_mode: {a.ap_mode}"]
     print("\n".join(lines[:12]))
     with open(a.output, "w") as f:
         f.write("\n".join(lines) + "\n")

@@ -8,6 +8,7 @@ from .models import YOLOv1, Backbone, DetectionHead, ResNetBackbone, YOLOv1Backb
 from .optim import ModelEMA  # noqa: F401  (weight EMA for training; the reference keeps none, so it stays out of __all__)
 from .optim import GradAccumulator  # noqa: F401  (K micro-batches per optimizer step; likewise)
 from .classify import GlobalAvgPool, SoftmaxCrossEntropy, YOLOv1Classifier  # noqa: F401  (classification pretraining of the trunk; likewise)
+from .voc_eval import VOCGroundTruth, VOCMetric, evaluate_voc  # noqa: F401  (the VOC devkit's evaluation protocol; likewise)
 from .schemas import BoundingBox, Detection
 
 # north_star spellings as aliases of the reference's names

@@ -164,6 +164,8 @@ _SIGS = {
                                  ctypes.c_long, ctypes.c_long, ctypes.c_long, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "yolo_map_match": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_int, ctypes.POINTER(c_double), c_int, c_double, c_double, c_double,
                        c_void_p, c_void_p, c_void_p],
+    "yolo_voc_match": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                       ctypes.POINTER(c_double), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "yolo_pairwise_iou": [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "yolo_loss_fwd_bwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "yolo_loss_iou": [c_void_p, c_void_p, c_long, c_void_p, c_void_p],

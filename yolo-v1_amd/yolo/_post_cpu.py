@@ -137,3 +137,61 @@ def nms_classes(groups: list, thr: float, variant: int):
     if variant == INFERENCE:
         keep = keep[np.argsort(-rec[keep, 1], kind="stable")]
     return rec.reshape(-1, 6), keep.astype(np.int32)
+
+
+# ------------------------------------------------------------------------------------------------
+# PASCAL VOC devkit matching ("VOC devkit evaluation"): what yolo_voc_match does on the device, array-wise per
+# (image, class) group -- the same float64 operations in the same order
+# ------------------------------------------------------------------------------------------------
+VOC_FP, VOC_TP, VOC_IGNORED = 0, 1, 2
+
+
+def voc_pixel_boxes(xywh: np.ndarray, W: float, H: float) -> np.ndarray:
+    """(n,4) normalised centre boxes -> (n,4) pixel corners of a W x H image, clamped to it."""
+    x, y, w, h = (np.asarray(xywh, np.float64).reshape(-1, 4)[:, k] for k in range(4))
+    W, H = np.float64(W), np.float64(H)
+    out = np.stack([(x - w / 2) * W, (y - h / 2) * H, (x + w / 2) * W, (y + h / 2) * H], 1)
+    for col, lim in ((0, W), (1, H), (2, W), (3, H)):
+        v = out[:, col]
+        v[v < 0] = 0.0
+        v[v > lim] = lim
+    return out
+
+
+def voc_match(kept: np.ndarray, W: float, H: float, gt_box: np.ndarray, gt_cls: np.ndarray, gt_difficult: np.ndarray, thresholds):
+    """One image.  ``kept`` (n,6): its kept records in metrics-NMS order (inside a class: score-descending).  Returns the status
+    words (n,) uint32 -- 2 bits per threshold: 0 FP, 1 TP, 2 ignored -- and the clamped pixel boxes (n,4)."""
+    kept = np.asarray(kept, np.float64).reshape(-1, 6)
+    box = voc_pixel_boxes(kept[:, 2:6], W, H)
+    status = np.zeros(len(kept), np.uint32)
+    thr = np.asarray(thresholds, np.float64)
+    shifts = (2 * np.arange(len(thr))).astype(np.uint32)
+    dcls = kept[:, 0].astype(np.int64)
+    for c in np.unique(dcls):
+        gi = np.nonzero(gt_cls == c)[0]
+        if len(gi) == 0:
+            continue                                                      # no candidate: FP at every threshold
+        di = np.nonzero(dcls == c)[0]
+        d, g, dif = box[di], gt_box[gi], gt_difficult[gi]
+        iw = np.where(g[None, :, 2] < d[:, None, 2], g[None, :, 2], d[:, None, 2]) - np.where(g[None, :, 0] > d[:, None, 0], g[None, :, 0], d[:, None, 0]) + 1
+        ih = np.where(g[None, :, 3] < d[:, None, 3], g[None, :, 3], d[:, None, 3]) - np.where(g[None, :, 1] > d[:, None, 1], g[None, :, 1], d[:, None, 1]) + 1
+        darea = (d[:, 2] - d[:, 0] + 1) * (d[:, 3] - d[:, 1] + 1)
+        garea = (g[:, 2] - g[:, 0] + 1) * (g[:, 3] - g[:, 1] + 1)
+        inter = iw * ih
+        part = (iw > 0) & (ih > 0)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            ov = np.where(part, inter / (darea[:, None] + garea[None, :] - inter), -np.inf)
+        jmax = ov.argmax(1)                                               # first of the largest
+        ovmax = ov[np.arange(len(di)), jmax]
+        taken = np.zeros((len(gi), len(thr)), bool)
+        for k in range(len(di)):                                          # the greedy walk, all thresholds at once
+            j = jmax[k]
+            hit = ovmax[k] >= thr
+            if dif[j]:
+                st = np.where(hit, VOC_IGNORED, VOC_FP)
+            else:
+                tp = hit & ~taken[j]
+                taken[j] |= tp
+                st = np.where(tp, VOC_TP, VOC_FP)
+            status[di[k]] = np.bitwise_or.reduce(st.astype(np.uint32) << shifts)
+    return status, box

@@ -71,6 +71,19 @@ class SyntheticYOLODataset(Dataset):
         cids = [int(rng.integers(0, self.C)) for _ in range(k)]
         return img, encode_target(boxes, cids, self.S, self.B, self.C)
 
+    def ground_truth(self, idx: int) -> dict:
+        """The sample's objects as an annotation would list them (yolo/voc_eval.py): ALL k boxes of ``__getitem__``'s generator, also
+        those ``encode_target`` drops because their cell is taken, as pixel corners of a size x size image; nothing is difficult."""
+        rng = np.random.Generator(np.random.PCG64([self.seed, idx]))
+        rng.standard_normal((3, self.size, self.size), dtype=np.float32)          # the image's draws come first
+        k = int(rng.integers(0, self.max_obj + 1))
+        boxes = [(*rng.uniform(0, 1, 2), *rng.uniform(0.05, 0.9, 2)) for _ in range(k)]
+        cids = [int(rng.integers(0, self.C)) for _ in range(k)]
+        size = float(self.size)
+        pix = [[(xc - w / 2) * size, (yc - h / 2) * size, (xc + w / 2) * size, (yc + h / 2) * size] for xc, yc, w, h in boxes]
+        return {"image_id": f"{idx:06d}", "width": self.size, "height": self.size, "boxes": np.array(pix, np.float64).reshape(-1, 4),
+                "class_ids": np.array(cids, np.int64), "difficult": np.zeros(k, bool)}
+
 
 # ------------------------------------------------------------------------------------------------------------------
 # PASCAL VOC on disk
@@ -452,6 +465,25 @@ class VOCDetectionYOLO(Dataset):
     def _encode_target(self, bboxes: list, class_ids: list) -> torch.Tensor:
         return encode_target(bboxes, class_ids, self.S, self.B, self.C)
 
+    def ground_truth(self, idx: int) -> dict:
+        """What the annotation file says, for the devkit's evaluation (yolo/voc_eval.py): every object with a known class name -- also the
+        ones that share a grid cell, which the target tensor cannot hold -- as pixel corners, with its ``difficult`` flag (0 where the tag
+        is missing).  Reads the XML only; the image is not opened."""
+        root = ET.parse(self.voc_dir / "Annotations" / f"{self.ids[idx]}.xml").getroot()
+        size = root.find("size")
+        boxes, class_ids, difficult = [], [], []
+        for obj in root.iter("object"):
+            name = (obj.findtext("name") or "").strip()
+            if name not in self.class_to_idx:
+                continue
+            bb = obj.find("bndbox")
+            boxes.append([float(bb.findtext(k)) for k in ("xmin", "ymin", "xmax", "ymax")])
+            class_ids.append(self.class_to_idx[name])
+            difficult.append(int((obj.findtext("difficult") or "0").strip() or 0) != 0)
+        return {"image_id": self.ids[idx], "width": int(float(size.findtext("width"))), "height": int(float(size.findtext("height"))),
+                "boxes": np.array(boxes, np.float64).reshape(-1, 4), "class_ids": np.array(class_ids, np.int64),
+                "difficult": np.array(difficult, bool)}
+
     def visualize_sample(self, idx: int) -> dict:
         image, annotation = self._load(idx)
         bboxes, class_ids = self._extract_bboxes_from_annotation(annotation)
@@ -483,6 +515,12 @@ class CombinedVOCDataset(Dataset):
             raise IndexError(f"Index {idx} out of range for dataset of size {len(self)}")
         k = int(np.searchsorted(self.cumulative_lengths, idx, side="right")) - 1
         return self.datasets[k][idx - self.cumulative_lengths[k]]
+
+    def ground_truth(self, idx: int) -> dict:
+        if idx < 0 or idx >= len(self):
+            raise IndexError(f"Index {idx} out of range for dataset of size {len(self)}")
+        k = int(np.searchsorted(self.cumulative_lengths, idx, side="right")) - 1
+        return self.datasets[k].ground_truth(idx - self.cumulative_lengths[k])
 
 
 def create_voc_datasets(years_and_splits: list, download: bool = True, S: int = 7, B: int = 2, target_size: Tuple[int, int] = (448, 448),

@@ -99,6 +99,58 @@ def map_match(rec: torch.Tensor, keep: torch.Tensor, kc: torch.Tensor, grec: tor
     return tp, bucket
 
 
+VOC_MAX_THRESHOLDS, VOC_MAX_GT, VOC_MAX_PER_GROUP = 16, 256, 1024      # the limits of yolo_voc_match (include/yolo_hip.h)
+
+
+class VocStaging:
+    """The five output buffers of ``yolo_voc_match`` for the worst case of one batch shape, kept by the caller across batches."""
+
+    def __init__(self, rows: int, device):
+        self.rows, self.device = rows, device
+        self.score = torch.empty((rows,), dtype=torch.float64, device=device)
+        self.cls_img = torch.empty((rows, 2), dtype=torch.int32, device=device)
+        self.status = torch.empty((rows,), dtype=torch.int32, device=device)         # the uint32 status words, bit for bit
+        self.box = torch.empty((rows, 4), dtype=torch.float64, device=device)
+        self.total = torch.empty((1,), dtype=torch.int32, device=device)
+
+
+@_hip.device_guard
+def voc_match(rec: torch.Tensor, keep: torch.Tensor, kc: torch.Tensor, groups_per_image: int, gt_box: np.ndarray, gt_cls: np.ndarray,
+              gt_difficult: np.ndarray, gt_off: np.ndarray, img_wh: np.ndarray, image_base: int, thresholds, staging: VocStaging = None):
+    """PASCAL VOC devkit matching of the kept detections of ``nms`` (metrics variant) on the device (see yolo_voc_match).
+    rec (n_groups, M, 6), keep (n_groups, M), kc (n_groups,) device tensors; the batch's slice of the ground-truth table as
+    HOST arrays -- gt_box (G,4) f64 pixel corners, gt_cls (G,), gt_difficult (G,), gt_off (images+1,) starting at 0, img_wh
+    (images,2) -- uploaded here in one copy.  Launches without synchronising; returns the staging buffers (``staging`` if it
+    is given and large enough), whose ``total`` says how many leading rows are valid."""
+    _hip.require_cuda(rec, keep, kc)
+    assert rec.dtype == torch.float64 and rec.is_contiguous() and keep.dtype == torch.int32 and keep.is_contiguous() and kc.dtype == torch.int32
+    n_groups, M, _ = rec.shape
+    gt_off = np.ascontiguousarray(gt_off, np.int32)
+    n_img, G = len(gt_off) - 1, int(gt_off[-1])
+    if n_img * groups_per_image != n_groups or gt_off[0] != 0 or len(gt_box) != G or len(gt_cls) != G or len(gt_difficult) != G or len(img_wh) != n_img:
+        raise RuntimeError(f"voc_match: {n_groups} groups of {groups_per_image} per image do not fit a ground-truth slice of {n_img} images, {G} rows")
+    max_gt = int(np.diff(gt_off).max()) if n_img else 0
+    # one upload: the f64 parts first, then the int32 parts, then the bytes (every part stays aligned to its type)
+    f64 = np.concatenate([np.asarray(gt_box, np.float64).reshape(-1), np.asarray(img_wh, np.float64).reshape(-1)])
+    i32 = np.concatenate([np.asarray(gt_cls, np.int32).reshape(-1), gt_off])
+    blob = np.concatenate([f64.view(np.uint8), i32.view(np.uint8), np.asarray(gt_difficult, np.uint8).reshape(-1), np.zeros(8, np.uint8)])
+    dev = torch.from_numpy(blob).to(rec.device)
+    p0 = dev.data_ptr()
+    p_box, p_wh = p0, p0 + 32 * G
+    p_cls = p0 + 8 * len(f64)
+    p_off = p_cls + 4 * G
+    p_dif = p_cls + 4 * len(i32)
+    if staging is None or staging.rows < n_groups * M or staging.device != rec.device:
+        staging = VocStaging(max(n_groups * M, 1), rec.device)
+    thr = (ctypes.c_double * len(thresholds))(*[float(t) for t in thresholds])
+    vp = ctypes.c_void_p
+    check(lib().yolo_voc_match(ptr(rec), ptr(keep), ptr(kc), n_groups, M, int(groups_per_image), vp(p_box), vp(p_cls), vp(p_dif), vp(p_off), vp(p_wh),
+                               max_gt, int(image_base), thr, len(thresholds), ptr(staging.score), ptr(staging.cls_img), ptr(staging.status),
+                               ptr(staging.box), ptr(staging.total), stream()), "yolo_voc_match")
+    staging.upload = dev          # the kernel reads it: it must outlive the launch
+    return staging
+
+
 def classes_to_images(rec_h, counts_h, keep_h, kc_h, variant: int, extra=None):
     """Host arrays of ``decode_classes`` + grouped ``nms`` -> per image (rec, keep) like ``_post_cpu.nms_classes``: the valid rows
     of the image's C groups one behind the other, and the kept indices into them in the result order of ``variant``.
