@@ -815,6 +815,32 @@ int yolo_voc_match(const double *rec, const int32_t *keep, const int32_t *keep_c
                    yolo_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The final answer of batched detection ("Batched detection"; not in the reference): the kept detections of
+ * yolo_decode / yolo_decode_classes + yolo_nms (variant YOLO_NMS_INFERENCE) as one dense list per image in result order, in
+ * one launch (one workgroup per image), so that the copy to the host is the detections and nothing else.
+ *   rec, keep, keep_counts   as yolo_nms takes and leaves them: n_groups groups of max_per_group records
+ *   groups_per_image         C behind yolo_decode_classes, 1 behind yolo_decode; group g belongs to image g / groups_per_image
+ *   img_wh [images][2] f64 = {W, H} in pixels, device memory, or NULL
+ * Result order of image n: the kept entries of its groups, groups ascending, each group in its keep order; with
+ * groups_per_image > 1 that list by score descending, equal scores in list order (numpy's stable argsort of -score, what
+ * yolo/ops.py: classes_to_images does on the host).  A merge by rank: every keep list of the inference variant is in that order
+ * already, which the kernel relies on.
+ *   out_det [total][6] f64 = {class, score, b0, b1, b2, b3}: with img_wh the pixel corners {xmin, ymin, xmax, ymax} clamped to
+ *           the image (fp64, the operations of yolo/_post_cpu.py: voc_pixel_boxes in their order), with img_wh == NULL the
+ *           record's x, y, w, h bit for bit
+ *   out_image [total] int32  the image of each row
+ *   out_off [images + 1] int32: image n owns rows out_off[n] .. out_off[n+1] - 1; out_off[images] = total
+ * Rows behind total are not written; the outputs hold n_groups * max_per_group rows at most.  No atomics: the same input gives
+ * the same bits.  The scores of an image are ranked out of LDS while groups_per_image * max_per_group <= 4096 (the default model:
+ * 20 x 98 = 1960); beyond that the same ranking reads them from global memory -- slower, the same result, no shape is refused.
+ * YOLO_E_ARG, before any HIP call: a null pointer (img_wh excepted), n_groups < 0, max_per_group < 1, groups_per_image < 1,
+ * n_groups not a multiple of groups_per_image.  YOLO_E_UNSUPPORTED: n_groups * max_per_group beyond int32.  n_groups == 0
+ * succeeds with out_off[0] = 0. */
+int yolo_detect_finish(const double *rec, const int32_t *keep, const int32_t *keep_counts, int n_groups, int max_per_group,
+                       int groups_per_image, const double *img_wh, double *out_det, int32_t *out_image, int32_t *out_off,
+                       yolo_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Image preprocessing.  Replaces YOLOInference.transform / the eval transform of the reference
  * (src/yolo/inference.py:58-66, src/yolo/dataset.py:224-233): Resize((Ho,Wo)) = PIL.Image.resize(BILINEAR) ->
  * ToTensor (/255) -> Normalize(mean, std), from decoded uint8 RGB [N][Hs][Ws][3] in device memory.

@@ -166,6 +166,7 @@ _SIGS = {
                        c_void_p, c_void_p, c_void_p],
     "yolo_voc_match": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                        ctypes.POINTER(c_double), c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
+    "yolo_detect_finish": [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p],
     "yolo_pairwise_iou": [c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p],
     "yolo_loss_fwd_bwd": [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_void_p, c_void_p, c_void_p, c_void_p],
     "yolo_loss_iou": [c_void_p, c_void_p, c_long, c_void_p, c_void_p],

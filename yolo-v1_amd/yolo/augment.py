@@ -79,6 +79,28 @@ class U8Batch:
         self._descs = self._descs_dev = None
         self._tmp_bytes = 0
 
+    @classmethod
+    def from_images(cls, images: Sequence, size=(448, 448), buffer: torch.Tensor = None) -> "U8Batch":
+        """The inference transform of decoded images of any sizes (uint8 (H, W, 3) arrays or tensors): the whole image as the
+        crop, no colour operation, no flip -- Resize(size) + ToTensor + Normalize, what ``YOLOInference.preprocess_image`` does.
+        ``buffer``: a flat uint8 host tensor (e.g. page-locked) at least as large as the images together; they are packed into
+        its head instead of a fresh buffer."""
+        arrays = [im.detach().cpu().numpy() if isinstance(im, torch.Tensor) else np.asarray(im) for im in images]
+        for a in arrays:
+            if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1 or a.shape[1] < 1:
+                raise ValueError(f"U8Batch.from_images expects uint8 images of shape (H, W, 3), got {a.dtype} {tuple(a.shape)}")
+        total = sum(a.size for a in arrays)
+        if buffer is None:
+            buffer = torch.empty(total, dtype=torch.uint8)
+        elif buffer.dtype != torch.uint8 or buffer.dim() != 1 or buffer.is_cuda or not buffer.is_contiguous() or buffer.numel() < total:
+            raise ValueError(f"buffer must be a flat uint8 host tensor of at least {total} bytes")
+        flat, off = buffer.numpy(), 0            # (shares the buffer's memory; the images may be read-only arrays)
+        for a in arrays:
+            flat[off: off + a.size] = a.reshape(-1)
+            off += a.size
+        sizes = [(a.shape[0], a.shape[1]) for a in arrays]
+        return cls(buffer[:total], sizes, [AugParams(0, 0, h, w) for h, w in sizes], size)
+
     # ------------------------------------------------------------------ tensor-like surface
     def __len__(self) -> int:
         return len(self.sizes)

@@ -1,13 +1,19 @@
-"""Single-image inference pipeline with the reference's surface (src/yolo/inference.py:12-317).
+"""Inference pipeline with the reference's single-image surface (src/yolo/inference.py:12-317), and batches of images.
 
 ``predict`` = load -> resize/normalise -> model -> decode -> NMS.  On a ROCm device the model runs on
 the HIP engine and decode + NMS run as two kernel launches with ONE device->host copy, instead of
 ~880 ``.item()`` syncs per image (inference.py:184-191).
+
+``predict_batch`` / ``predict_batch_arrays`` take a list of files, PIL images or decoded arrays of any sizes (DESIGN.md,
+"Batched detection"): a thread pool decodes batch k + 1 while batch k runs, a batch is uploaded as one packed uint8 buffer
+(``yolo.augment.U8Batch``) and resized on the device, and decode + NMS + ``yolo_detect_finish`` leave the per-image result lists
+on the device, so the copy back is the detections alone.
 """
 
 from __future__ import annotations
 
 import warnings
+from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 import torch
@@ -40,6 +46,11 @@ class _Preprocess:
             arr = arr[:, :, None]
         t = torch.from_numpy(arr.copy()).permute(2, 0, 1).to(torch.float32).div_(255.0)
         return (t - self.mean) / self.std
+
+
+def _clamp_workers(workers: int) -> int:
+    """decoder threads of ``predict_batch``: what the caller asks for within 1 .. 16, never the machine's CPU count"""
+    return max(1, min(16, int(workers)))
 
 
 def _default_device() -> str:
@@ -80,7 +91,10 @@ class YOLOInference:
         """scoring="all": the paper's test-time protocol -- every box scored for every class, NMS per class, the kept detections
         of all classes by confidence (a box may come out under several classes)."""
         _post_cpu.check_scoring(scoring)
-        image = self.load_image(image_path)
+        return self._predict_loaded(self.load_image(image_path), conf_threshold, nms_threshold, class_names, scoring)
+
+    def _predict_loaded(self, image: Image.Image, conf_threshold: float, nms_threshold: float, class_names, scoring: str) -> list[Detection]:
+        """``predict`` behind ``load_image``"""
         x = self.preprocess_image(image)
         with torch.no_grad():
             pred = self.model(x)
@@ -107,6 +121,131 @@ class YOLOInference:
             out.append(Detection(class_id=cid, class_name=class_names[cid] if class_names else f"class_{cid}",
                                  confidence=conf, bbox=BoundingBox(x=x, y=y, width=w, height=h)))
         return out
+
+    # ------------------------------------------------------------------ batches
+    def predict_batch(self, images, conf_threshold: float = 0.5, nms_threshold: float = 0.4, class_names: list[str] | None = None,
+                      scoring: str = "argmax", batch_size: int = 64, workers: int = 4) -> list[list[Detection]]:
+        """``predict`` for many images -- paths, PIL images or uint8 (H, W, 3) arrays in any mix, of any sizes: per image, in input
+        order, the detections ``predict`` would return.  On a device the files are decoded by ``workers`` threads while the previous
+        batch runs, a batch travels as one packed uint8 buffer, and decode + NMS + the per-image result lists are three launches whose
+        output -- the detections and nothing else -- is all that is copied back.  A CPU model takes the images one by one."""
+        _post_cpu.check_scoring(scoring)
+        images = list(images)
+        if not self._on_gpu():
+            return [self._predict_loaded(im, conf_threshold, nms_threshold, class_names, scoring) for im in self._loaded(images, workers)]
+        out = []
+        for det, off, _ in self._device_batches(images, conf_threshold, nms_threshold, scoring, batch_size, workers, pixels=False):
+            dets = self._records_to_detections(det, class_names)     # validates every box like the reference
+            out += [dets[off[n]: off[n + 1]] for n in range(len(off) - 1)]
+        return out
+
+    def predict_batch_arrays(self, images, conf_threshold: float = 0.5, nms_threshold: float = 0.4, class_names: list[str] | None = None,
+                             scoring: str = "argmax", batch_size: int = 64, workers: int = 4, normalized: bool = False):
+        """``predict_batch`` for bulk callers: (image_index (n,) int32, class_id (n,) int32, score (n,) f64, pixel_boxes (n, 4) f64
+        {xmin, ymin, xmax, ymax} clamped to the image, sizes (images, 2) int32 {W, H}), rows in input order of the images and
+        result order inside an image.  ``normalized``: a sixth array (n, 4), the boxes as ``predict`` reports them {x, y, w, h}.
+        ``class_names`` is accepted for the common signature and not used."""
+        _post_cpu.check_scoring(scoring)
+        images = list(images)
+        det, norm, idx, sizes = [np.zeros((0, 6))], [np.zeros((0, 4))], [np.zeros(0, np.int32)], [np.zeros((0, 2), np.int32)]
+        if not self._on_gpu():
+            for i, im in enumerate(self._loaded(images, workers)):
+                ds = self._predict_loaded(im, conf_threshold, nms_threshold, None, scoring)
+                box = np.array([[d.bbox.x, d.bbox.y, d.bbox.width, d.bbox.height] for d in ds], np.float64).reshape(-1, 4)
+                head = np.array([[d.class_id, d.confidence] for d in ds], np.float64).reshape(-1, 2)
+                det.append(np.concatenate([head, _post_cpu.voc_pixel_boxes(box, im.width, im.height)], 1))
+                norm.append(box)
+                idx.append(np.full(len(ds), i, np.int32))
+                sizes.append(np.array([[im.width, im.height]], np.int32))
+        else:
+            base = 0
+            for d, off, wh, *xywh in self._device_batches(images, conf_threshold, nms_threshold, scoring, batch_size, workers, pixels=True,
+                                                          both=normalized):
+                det.append(d)
+                norm += xywh
+                idx.append(np.repeat(np.arange(base, base + len(wh), dtype=np.int32), np.diff(off)))
+                sizes.append(wh)
+                base += len(wh)
+        det = np.concatenate(det)
+        res = (np.concatenate(idx), det[:, 0].astype(np.int32), det[:, 1].copy(), det[:, 2:6].copy(), np.concatenate(sizes))
+        return res + (np.concatenate(norm),) if normalized else res
+
+    @staticmethod
+    def _decoded(item):
+        """path -> RGB PIL image (the caller's ``load_image``); PIL image -> RGB; uint8 (H, W, 3) array or tensor -> itself"""
+        if isinstance(item, Image.Image):
+            return item if item.mode == "RGB" else item.convert("RGB")
+        if isinstance(item, torch.Tensor):
+            item = item.detach().cpu().numpy()
+        if isinstance(item, np.ndarray):
+            if item.dtype != np.uint8 or item.ndim != 3 or item.shape[2] != 3:
+                raise ValueError(f"predict_batch takes uint8 images of shape (H, W, 3), got {item.dtype} {item.shape}")
+            return item
+        return None
+
+    def _load_one(self, item):
+        """one input of ``predict_batch`` decoded: a PIL RGB image or a uint8 (H, W, 3) array; runs in a worker thread"""
+        got = self._decoded(item)
+        if got is not None:
+            return got
+        try:
+            return self.load_image(item)
+        except Exception as e:
+            raise RuntimeError(f"predict_batch: cannot read image {str(item)!r}: {e}") from e
+
+    def _loaded(self, images, workers: int):
+        """CPU path: every input as a PIL RGB image, decoded by the pool ahead of the loop; the pool is gone when this returns"""
+        with ThreadPoolExecutor(max_workers=_clamp_workers(workers)) as pool:
+            futures = [pool.submit(self._load_one, im) for im in images]
+            try:
+                return [im if isinstance(im, Image.Image) else Image.fromarray(im) for im in (f.result() for f in futures)]
+            except BaseException:
+                pool.shutdown(wait=True, cancel_futures=True)
+                raise
+
+    def _device_batches(self, images, conf_threshold, nms_threshold, scoring, batch_size, workers, pixels: bool, both: bool = False):
+        """The host pipeline of ``predict_batch`` on a device; yields per batch (det (rows, 6), off (images + 1,), sizes (images, 2)
+        {W, H}[, xywh (rows, 4) if ``both``]) as NumPy arrays; det holds pixel corners if ``pixels`` else the records' x, y, w, h.
+        At most two batches are in flight: batch k + 1 is decoded by the pool while batch k runs.  The packed images go through two
+        page-locked staging buffers in turn, each rewritten only after an event recorded behind its upload has completed; uploads and
+        kernels share the current stream."""
+        from . import ops
+        from .augment import U8Batch
+        if batch_size < 1:
+            raise ValueError("batch_size must be at least 1")
+        model, dev = self.model, torch.device(self.device)
+        S, B = model.S, model.B
+        fused = hasattr(model, "_fusable") and model._fusable()
+        size = self.transform.size if isinstance(self.transform, _Preprocess) else (448, 448)
+        chunks = [images[i: i + batch_size] for i in range(0, len(images), batch_size)]
+        staging, uploaded = [None, None], [None, None]
+        pool = ThreadPoolExecutor(max_workers=_clamp_workers(workers))
+        try:
+            submit = lambda chunk: [pool.submit(self._load_one, im) for im in chunk]
+            pending = submit(chunks[0]) if chunks else None
+            for k in range(len(chunks)):
+                following = submit(chunks[k + 1]) if k + 1 < len(chunks) else None      # decoded while batch k runs
+                arrays = [np.asarray(im, dtype=np.uint8) for im in (f.result() for f in pending)]
+                pending = following
+                slot, need = k % 2, sum(a.size for a in arrays)
+                if uploaded[slot] is not None:
+                    uploaded[slot].synchronize()
+                if staging[slot] is None or staging[slot].numel() < need:
+                    staging[slot] = torch.empty(need + need // 4, dtype=torch.uint8, pin_memory=True)
+                with torch.cuda.device(dev), torch.no_grad():
+                    batch = U8Batch.from_images(arrays, size, buffer=staging[slot]).to(dev, non_blocking=True)
+                    uploaded[slot] = torch.cuda.Event()
+                    uploaded[slot].record()
+                    pred = model(batch if fused else batch.to_tensor())
+                    wh = np.array([[a.shape[1], a.shape[0]] for a in arrays], np.int32)
+                    rec, keep, kc, gpi = ops._groups(pred, conf_threshold, nms_threshold, ops._hip.NMS_INFERENCE, S, B, pred.shape[-1] - 5 * B, scoring)
+                    first = ops.detect_finish(rec, keep, kc, gpi, wh if pixels else None)
+                    second = ops.detect_finish(rec, keep, kc, gpi, None) if pixels and both else None
+                    det, off = ops.rows_to_host(first[0], first[2])
+                    out = (det, off, wh) + ((second[0][: len(det), 2:6].cpu().numpy(),) if second is not None else ())
+                yield out          # (outside the no_grad / device scopes: they must not stay entered while the caller runs)
+        finally:
+            pool.shutdown(wait=True, cancel_futures=True)
 
     def parse_predictions(self, pred: torch.Tensor, conf_threshold: float, class_names: list[str] | None = None,
                           scoring: str = "argmax") -> list[Detection]:

@@ -190,6 +190,64 @@ def postprocess_host(pred: torch.Tensor, conf_thr: float, nms_thr: float, varian
     return [(rec_h[n, : counts_h[n]], keep_h[n, : kc_h[n]]) for n in range(rec_h.shape[0])]
 
 
+def _groups(pred: torch.Tensor, conf_thr: float, nms_thr: float, variant: int, S: int, B: int, C: int, scoring: str):
+    """decode + NMS of a batch as ``yolo_voc_match`` / ``yolo_detect_finish`` take them: rec (n_groups, M, 6), keep (n_groups, M),
+    keep counts (n_groups,), groups per image (C under scoring "all", else 1)"""
+    from ._post_cpu import check_scoring
+    if check_scoring(scoring) == "all":
+        rec, counts = decode_classes(pred, conf_thr, S, B, C)
+        rec, counts, gpi = rec.view(-1, S * S * B, 6), counts.view(-1), C
+    else:
+        (rec, counts), gpi = decode(pred, conf_thr, S, B, C), 1
+    keep, kc = nms(rec, counts, nms_thr, variant)
+    return rec, keep, kc, gpi
+
+
+@_hip.device_guard
+def detect_finish(rec: torch.Tensor, keep: torch.Tensor, kc: torch.Tensor, groups_per_image: int, img_wh=None):
+    """The kept detections of ``nms`` (inference variant) as dense per-image lists in result order (see yolo_detect_finish).
+    ``img_wh`` (images, 2) {W, H}, array or tensor: pixel corners clamped to the image; None: the records' x, y, w, h.
+    Returns device tensors det (rows, 6) f64, image (rows,) i32, off (images + 1,) i32 sized for the worst case: the first
+    ``off[-1]`` rows are valid, the rest is not written."""
+    _hip.require_cuda(rec, keep, kc)
+    assert rec.dtype == torch.float64 and rec.is_contiguous() and keep.dtype == torch.int32 and keep.is_contiguous() and kc.dtype == torch.int32
+    n_groups, M, _ = rec.shape
+    if groups_per_image < 1 or n_groups % groups_per_image:
+        raise RuntimeError(f"detect_finish: {n_groups} groups are not a multiple of {groups_per_image} per image")
+    n_img = n_groups // groups_per_image
+    if img_wh is not None:
+        img_wh = torch.as_tensor(img_wh, dtype=torch.float64).to(rec.device).contiguous()
+        if tuple(img_wh.shape) != (n_img, 2):
+            raise RuntimeError(f"detect_finish: img_wh {tuple(img_wh.shape)} must be ({n_img}, 2)")
+    det = torch.empty((max(n_groups * M, 1), 6), dtype=torch.float64, device=rec.device)
+    image = torch.empty((max(n_groups * M, 1),), dtype=torch.int32, device=rec.device)
+    off = torch.empty((n_img + 1,), dtype=torch.int32, device=rec.device)
+    check(lib().yolo_detect_finish(ptr(rec), ptr(keep), ptr(kc), n_groups, M, int(groups_per_image), ptr(img_wh), ptr(det), ptr(image), ptr(off),
+                                   stream()), "yolo_detect_finish")
+    return det, image, off
+
+
+def detect(pred: torch.Tensor, conf_thr: float, nms_thr: float, S: int, B: int, C: int, scoring: str = "argmax", img_wh=None):
+    """Batched detection on the device: decode, NMS (inference variant) and ``detect_finish`` as three launches, no
+    synchronisation.  Returns the device tensors (det, image, off) of ``detect_finish``."""
+    rec, keep, kc, gpi = _groups(pred, conf_thr, nms_thr, _hip.NMS_INFERENCE, S, B, C, scoring)
+    return detect_finish(rec, keep, kc, gpi, img_wh)
+
+
+def rows_to_host(det: torch.Tensor, off: torch.Tensor):
+    """(det, off) of ``detect_finish`` as NumPy arrays in two small copies: ``off`` first, then exactly ``off[-1]`` rows"""
+    off_h = off.cpu().numpy()
+    return det[: int(off_h[-1])].cpu().numpy(), off_h
+
+
+def detect_host(pred: torch.Tensor, conf_thr: float, nms_thr: float, S: int, B: int, C: int, scoring: str = "argmax", img_wh=None):
+    """``detect`` with the result on the host: (det (total, 6) f64, image (total,) i32, off (images + 1,) i32) as NumPy arrays.
+    Two small device->host copies -- ``off``, then exactly ``total`` rows; ``image`` is ``off`` spelled out per row."""
+    det, _, off = detect(pred, conf_thr, nms_thr, S, B, C, scoring, img_wh)
+    det_h, off_h = rows_to_host(det, off)
+    return det_h, np.repeat(np.arange(len(off_h) - 1, dtype=np.int32), np.diff(off_h)), off_h
+
+
 # ------------------------------------------------------------------------------------------------
 # loss
 # ------------------------------------------------------------------------------------------------
